@@ -7,7 +7,7 @@ Adam — config 3 of BASELINE.json.  `--config 2` runs the reference's no-tempor
 (train_coco2014.py: content + Gram style on the 2B single frames of B pairs).  Random-init weights
 (no checkpoint download offline), synthetic data already resident in HBM.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one rank per GPU, RCCL all-reduce)
 
 `python bench.py --gpus N` with N > 1 outside torchrun starts the N ranks itself: before any GPU
@@ -26,7 +26,19 @@ product on three-way split bf16 MFMAs, per-product error ~2^-24 (fp32-class; the
 golden steps pass at the f32 bar under it, tests/test_gpu_parity.py) at 2500/6 = 417 TFLOP/s
 peak; `f32` is exact fp32 MFMA (157.3 TFLOP/s).
 
-Prints ONE JSON line (rank 0).  `value` comes from K uninstrumented steps.  `roofline` = the
+Prints ONE JSON line (rank 0).  `value` comes from K uninstrumented steps.  A plain run does only
+what that headline needs: it stages the inputs, warms up, times the K steps, takes one instrumented
+step (the `dtype` label names the arithmetic of the conv launches it saw) and prints the line.
+`--dump-outputs DIR` writes what the last timed step handed its caller, as DIR/<name>.npy (float32):
+the step's returned loss terms, and `params`, the flattened model parameters it left behind
+(inference: `frames`; dataprep: `img`, `flow`, `mask`); at most 64 MB in all, a larger array as a
+fixed seeded sample of its elements.  Same arguments, same inputs, so two builds compare output for
+output.  (Measured, config 3, two processes of one build: after 1 step every array is bitwise equal;
+after 5 the loss terms differ by <= 6e-7 relative, after 105 by up to 2e-2 -- later steps do not
+repeat bitwise, and training from random weights at a loss of 1e10 amplifies the difference, so
+compare builds on few steps.)
+
+`--full` adds everything else, as extra keys of the same line.  `roofline` = the
 dominant kernel family (conv_gemm_kernel: conv forward + data-gradient implicit GEMM),
 algorithmic FLOPs / HIP-event-timed launch time over a second, instrumented run of the same step
 (events on the launching stream around every launch) vs the peak of the arithmetic launched.
@@ -59,17 +71,25 @@ def parse():
                     help="CPU stand-in step over gloo (tests the multi-rank launcher and timing without GPUs)")
     ap.add_argument("--steps", type=int, default=150)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--prof-steps", type=int, default=10, help="instrumented steps for the roofline line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the roofline of the dominant kernel "
+                         "family, the VGG19 sub-benchmark, the CPU baseline and the full-size parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
+    ap.add_argument("--prof-steps", type=int, default=None,
+                    help="instrumented steps for the roofline line (--full; default 10).  A plain run takes one, "
+                         "after its timed steps, to read the dtype label off the launches; 0 skips it")
     ap.add_argument("--model", default="reconet", choices=("reconet", "adaattn", "reconet_infer", "dataprep"),
                     help="reconet: BASELINE configs 2/3 (the metric); adaattn: config 4's train_video step")
     ap.add_argument("--batch", type=int, default=None, help="frame pairs per GPU (default 8 reconet, 4 adaattn)")
     ap.add_argument("--height", type=int, default=256)
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--config", type=int, default=3, choices=(2, 3))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline and the full-size parity that rests on it")
     ap.add_argument("--replay-input", action="store_true",
                     help="A/B only: replay the first synthetic batch every step instead of one batch per step")
-    ap.add_argument("--no-vgg19", action="store_true", help="skip the VGG19 fwd+dgrad north-star sub-benchmark")
+    ap.add_argument("--no-vgg19", action="store_true", help="with --full: skip the VGG19 fwd+dgrad north-star sub-benchmark")
     ap.add_argument("--cpu-threads", type=int, default=None,
                     help="oracle threads (default: os.cpu_count(), capped by OMP_NUM_THREADS = the box's CPU share)")
     ap.add_argument("--cpu-steps", type=int, default=5, help="timed oracle steps (median)")
@@ -78,7 +98,12 @@ def parse():
                     help="GEMM arithmetic policy, a name in vst.ops.POLICIES (bf16x6, f32, parity, bf16x3, bf16, "
                          "f16); default bf16x6 (fp32-class split products), f16 for the config-5 AdaAttN shape "
                          "(BASELINE's half-precision path)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.full:
+        args.prof_steps = 10 if args.prof_steps is None else args.prof_steps
+    else:  # one instrumented step labels the arithmetic (`dtype`); `--prof-steps 0` goes without
+        args.prof_steps = 1 if args.prof_steps is None else min(args.prof_steps, 1)
+    return args
 
 
 def cpu_threads(args):
@@ -519,7 +544,7 @@ def build_reconet_infer(args, dev, rank):
             x = ops.frames_to_tensor(frames)
             *_, y = model(x)
             ops.tensor_to_frames(y, frames=out)
-        return {}
+        return {"frames": out}
 
     return step
 
@@ -575,6 +600,7 @@ def run_dataprep(args, dev, rank, world):
         ops.flow_prep(flows, False, (Wo, Ho), out=fl)
         mask = ops.flow_warp_mask(fl[:B], fl[B:])
         ops.apply_motion_mask(mask, motion)
+        return {"img": img, "flow": fl, "mask": mask}
 
     for _ in range(args.warmup):
         step()
@@ -583,8 +609,9 @@ def run_dataprep(args, dev, rank, world):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    out = None
     for _ in range(args.steps):
-        step()
+        out = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -592,20 +619,22 @@ def run_dataprep(args, dev, rank, world):
     if world > 1:
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed = float(elapsed.item())
-    # dominant kernel: the Pillow-exact frame resize, timed with HIP events on its own stream
-    st = torch.cuda.current_stream()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    reps = 20
-    e0.record(st)
-    for _ in range(reps):
-        resize_frames()
-    e1.record(st)
-    torch.cuda.synchronize()
-    us = 1e3 * e0.elapsed_time(e1) / reps
-    algo = 2 * B * (Hs * Ws * 3 + 3 * Ho * Wo * 4)  # uint8 HWC frames in, fp32 planes out
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out or {})
+    if args.full:
+        # dominant kernel: the Pillow-exact frame resize, timed with HIP events on its own stream
+        st = torch.cuda.current_stream()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        reps = 20
+        e0.record(st)
+        for _ in range(reps):
+            resize_frames()
+        e1.record(st)
+        torch.cuda.synchronize()
+        us = 1e3 * e0.elapsed_time(e1) / reps
+        algo = 2 * B * (Hs * Ws * 3 + 3 * Ho * Wo * 4)  # uint8 HWC frames in, fp32 planes out
     if rank != 0:
         return None
-    traffic, traffic_src = pmc_traffic("dataprep", "pil_resize_kernel<3, 5, 5>")
     result = {
         "metric": "frame-pair items/sec, FlyingThings3D __getitem__ device half (960x540 -> 640x360)",
         "value": B * world * args.steps / elapsed, "unit": "items/s", "n_gpus": world, "steps": args.steps,
@@ -616,12 +645,14 @@ def run_dataprep(args, dev, rank, world):
         "config": {"workload": f"dataprep: B={B} items/GPU, frames+motion 960x540 uint8, PFM flows 960x540x3 "
                                f"-> img1/img2 3x360x640, flow 2x360x640, mask 360x640", "global_batch": B * world,
                    "parallelism": f"dp{world}"},
-        "roofline": {"bound": "hbm", "kernel": "pil_resize_kernel<3, 5, 5> (frames, mode 0)",
-                     "achieved": algo / us / 1e3, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": algo / us / 1e3 / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                     "algo_bytes_per_launch": algo, "avg_launch_us": us},
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        traffic, traffic_src = pmc_traffic("dataprep", "pil_resize_kernel<3, 5, 5>")
+        result["roofline"] = {"bound": "hbm", "kernel": "pil_resize_kernel<3, 5, 5> (frames, mode 0)",
+                              "achieved": algo / us / 1e3, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                              "frac": algo / us / 1e3 / HBM_PEAK_GBS, "traffic": traffic,
+                              "traffic_source": traffic_src, "algo_bytes_per_launch": algo, "avg_launch_us": us}
+    if args.full and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_dataprep(args)
     print(json.dumps(result), flush=True)
     return result
@@ -676,6 +707,41 @@ def arithmetic_label(ops, ks):
 def _sync(dev):
     if dev.type == "cuda":
         torch.cuda.synchronize()
+
+
+DUMP_BYTES = 60_000_000  # all files of one --dump-outputs (the limit is 64 MB; headers and slack)
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy, float32 (float64 stays).  If all of it would exceed
+    DUMP_BYTES, every array larger than an equal share keeps that many of its elements: a sample of
+    its flattened index, numpy PCG64 seeded 0, drawn with replacement and sorted (the same for the
+    same shapes)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for k, v in arrays.items():
+        v = v.detach()
+        host[k] = v.to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu().numpy()
+    share = None
+    if sum(a.nbytes for a in host.values()) > DUMP_BYTES:
+        share = DUMP_BYTES // 8 // len(host)  # elements, at float64's size
+    for k, a in host.items():
+        if share is not None and a.size > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, share))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k.replace("/", "_") + ".npy"), a)
+
+
+def step_outputs(step, out):
+    """What a caller of the timed step holds after it: the tensors it returned and, for a training
+    step, the model parameters it updated (flattened in named_parameters order)."""
+    arrays = {k: v for k, v in (out or {}).items() if isinstance(v, torch.Tensor)}
+    trainer = getattr(step, "trainer", None)
+    if trainer is not None:
+        arrays["params"] = torch.cat([p.detach().reshape(-1) for p in trainer.model.parameters()])
+    return arrays
 
 
 def timed(step, steps, world, dev, mark=False):
@@ -737,13 +803,15 @@ def dry_run(args, world, rank):
             a.copy_(torch.tanh(a @ a) * 0.5)
         if world > 1:
             dist.all_reduce(grad)
-        return {}
+        return {"state": a}
 
     for _ in range(args.warmup):
         step()
-    elapsed, _ = timed(step, args.steps, world, dev)
+    elapsed, out = timed(step, args.steps, world, dev)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(step, out))
     value = B * world * args.steps / elapsed
     result = {"metric": "dry run (CPU stand-in step; launcher test)", "value": value, "unit": "frame-pairs/s",
               "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -802,7 +870,10 @@ def main():
         step()
     # headline: K uninstrumented steps
     elapsed, out = timed(step, args.steps, world, dev, mark=True)
-    # roofline: a second run of the same step with HIP events around every conv_gemm launch, the side
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(step, out))
+    # roofline (--full; a plain run takes one such step, for the dtype label alone): a second run
+    # of the same step with HIP events around every conv_gemm launch, the side
     # streams off so that each launch has the chip to itself: its duration is
     # the kernel's, not shared with a concurrent weight-gradient GEMM (the timed region above runs them
     # on; tools/gpu_r04_close.sh profiles with the same switches so the rocprofv3 averages compare)
@@ -820,11 +891,6 @@ def main():
     result = None
     if rank == 0:
         value = B * world * args.steps / elapsed
-        achieved = ks["tflops"]
-        c5 = args.model == "adaattn" and (H, W) == (512, 1024)
-        # the counter summary of this very workload and policy (the strict-f32 line has its own)
-        tag = "adaattn_c5" if c5 else (f"{args.model}_f32" if args.gemm == "f32" else args.model)
-        traffic, traffic_src = pmc_traffic(tag)
         if args.model == "reconet":
             metric = "training frame-pairs/sec at 256\u00d7512, ReCoNet+VGG19 loss, 1/2/4/8 GPUs"
             workload = (f"config{args.config}: ReCoNet {'train_candy step, full loss incl. FTL/OTL warp' if args.config == 3 else 'train_coco2014 step (content + Gram style, no temporal) on the 2B frames'}"
@@ -860,35 +926,42 @@ def main():
                        "global_batch": B * world, "height": H, "width": W, "parallelism": f"dp{world}"},
             "frames_per_s": 2 * value,
             "loss_last_step": loss,
-            "roofline": {"bound": "mfma", "kernel": "conv fwd + dgrad implicit GEMM (conv_halo_kernel: 3x3 stride-1 "
-                                                           "convs; conv_gemm_kernel: the rest), all tile variants",
-                         "achieved": achieved, "peak": ks["peak_tflops"], "unit": "TFLOP/s",
-                         "frac": achieved / ks["peak_tflops"], "traffic": traffic,
-                         "peak_note": "algorithmic fp32-operand TFLOP/s vs the MFMA peak of the arithmetic launched "
-                                      "(f32 157.3, bf16x6 2500/6, bf16x3 2500/3, bf16 2500; a mix: flops / "
-                                      "sum(flops_i / peak_i))",
-                         "frac_of_fp32_mfma_peak": achieved / FP32_MFMA_PEAK_TFLOPS,
-                         "by_mode": {ops.gemm_mode_name(m): v for m, v in ks["by_mode"].items()},
-                         "traffic_source": traffic_src,
-                         "algo_bytes_per_launch": ks["bytes"] / max(ks["launches"], 1),
-                         "launches": ks["launches"], "avg_launch_us": ks["avg_us"],
-                         "algo_gflop_per_launch": ks["flops"] / max(ks["launches"], 1) / 1e9,
-                         "measured_over": f"{args.prof_steps} instrumented steps after the timed region, side streams off "
-                                          f"({1e3 * prof_elapsed / max(args.prof_steps, 1):.2f} ms/step instrumented)",
-                         "share_of_step": ks["total_ms"] / max(1e3 * prof_elapsed, 1e-9)},
         }
         trainer = getattr(step, "trainer", None)
         if getattr(trainer, "scaler", None) is not None:
             # the fp16 dynamic loss scale after the run: skipped (overflowed) steps did no update
             result["loss_scaler"] = trainer.scaler.state_dict()
-        wg = timer.summary("wgrad")
-        if wg["launches"]:
-            result["roofline"]["wgrad_kernel"] = {"achieved": wg["tflops"], "peak": wg["peak_tflops"],
-                                                  "frac": wg["tflops"] / wg["peak_tflops"],
-                                                  "share_of_step": wg["total_ms"] / max(1e3 * prof_elapsed, 1e-9)}
         if args.model == "reconet_infer":
             del result["frames_per_s"]
-        if world == 1 and not args.no_vgg19 and args.model != "reconet_infer":
+        if args.full:
+            achieved = ks["tflops"]
+            c5 = args.model == "adaattn" and (H, W) == (512, 1024)
+            # the counter summary of this very workload and policy (the strict-f32 line has its own)
+            tag = "adaattn_c5" if c5 else (f"{args.model}_f32" if args.gemm == "f32" else args.model)
+            traffic, traffic_src = pmc_traffic(tag)
+            result["roofline"] = {
+                "bound": "mfma", "kernel": "conv fwd + dgrad implicit GEMM (conv_halo_kernel: 3x3 stride-1 "
+                                           "convs; conv_gemm_kernel: the rest), all tile variants",
+                "achieved": achieved, "peak": ks["peak_tflops"], "unit": "TFLOP/s",
+                "frac": achieved / ks["peak_tflops"], "traffic": traffic,
+                "peak_note": "algorithmic fp32-operand TFLOP/s vs the MFMA peak of the arithmetic launched "
+                             "(f32 157.3, bf16x6 2500/6, bf16x3 2500/3, bf16 2500; a mix: flops / "
+                             "sum(flops_i / peak_i))",
+                "frac_of_fp32_mfma_peak": achieved / FP32_MFMA_PEAK_TFLOPS,
+                "by_mode": {ops.gemm_mode_name(m): v for m, v in ks["by_mode"].items()},
+                "traffic_source": traffic_src,
+                "algo_bytes_per_launch": ks["bytes"] / max(ks["launches"], 1),
+                "launches": ks["launches"], "avg_launch_us": ks["avg_us"],
+                "algo_gflop_per_launch": ks["flops"] / max(ks["launches"], 1) / 1e9,
+                "measured_over": f"{args.prof_steps} instrumented steps after the timed region, side streams off "
+                                 f"({1e3 * prof_elapsed / max(args.prof_steps, 1):.2f} ms/step instrumented)",
+                "share_of_step": ks["total_ms"] / max(1e3 * prof_elapsed, 1e-9)}
+            wg = timer.summary("wgrad")
+            if wg["launches"]:
+                result["roofline"]["wgrad_kernel"] = {"achieved": wg["tflops"], "peak": wg["peak_tflops"],
+                                                      "frac": wg["tflops"] / wg["peak_tflops"],
+                                                      "share_of_step": wg["total_ms"] / max(1e3 * prof_elapsed, 1e-9)}
+        if args.full and world == 1 and not args.no_vgg19 and args.model != "reconet_infer":
             # SURVEY §8(d) sub-metric (>= 60 % of the MFMA roofline of the chosen precision) under exact
             # fp32 MFMA, and under the step's own policy for comparison
             ops.use_policy("f32")
@@ -901,7 +974,7 @@ def main():
                     "gemm_policy": args.gemm, **{k: v[k] for k in ("conv_tflops", "peak_tflops", "conv_frac",
                                                                     "wall_tflops", "wall_frac", "ms")}}
             ops.use_policy(args.gemm)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if args.model == "reconet":
                 result["cpu_baseline"], first = cpu_baseline(args)
                 result["full_size_parity"] = full_size_parity(args, dev, first)

@@ -432,7 +432,7 @@ def test_train_video_step_reduced_policy(golden, policy):
 
 # ----------------------------------------------------------------------------- mid-size (128x256)
 # At the golden step's 64x128 the relu3_1 attention has Ns = 512 style positions; here 2,048 (config
-# 4: 8,192; config 5: 32,768 -- bench.py --model adaattn reports the same check at those sizes in
+# 4: 8,192; config 5: 32,768 -- bench.py --full --model adaattn reports the same check at those sizes in
 # its `full_size_parity`).  The linear-form cosine attention re-associates bmm(A, V) / bmm(A, V^2)
 # into sums over all Ns and then forms E2 - M^2, so its error is measured where it is most sensitive:
 # each level's M and S against the float64 exact moments of the SAME Q, K, V, next to the
