@@ -82,8 +82,8 @@ def main():
             for s in SHAPES:
                 name, N, Cin, H, W, Cout, k, stride, gm, pad, up = s
                 x, dy, dw, ws, Ho, Wo, fl = bufs[name]
-                args = (dy.data_ptr(), x.data_ptr(), dw.data_ptr(), ws.data_ptr(), N, Cin, H, W, Cout, Ho, Wo, k, k, gm,
-                        stride, pad, up, 0, MODE, st)
+                args = (dy.data_ptr(), x.data_ptr(), dw.data_ptr(), ws.data_ptr(), ws.numel(), N, Cin, H, W, Cout, Ho, Wo,
+                        k, k, gm, stride, pad, up, 0, MODE, st)
                 if name.endswith("_p"):
                     args = (dy.data_ptr(), x.data_ptr(), dw.data_ptr(), ws.data_ptr(), N, Cin, H, W, Cout, 0, MODE, st)
                     fn = lib.vst_conv_wgrad_up2

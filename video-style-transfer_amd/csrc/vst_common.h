@@ -195,7 +195,7 @@ __device__ __forceinline__ void apack_store(float* out, int k, int m, int Mpad, 
 
 // One 16-deep k-tile of a wave's TM x TN block of 32x32 accumulators from bf16 LDS rows
 // ([hi k0..15][lo k0..15][pad], 20 dwords): rows a0 + 32i + lane&31 of A, b0 + 32j + lane&31 of B.
-template <int TM, int TN, int PREC, int LS>
+template <int TM, int TN, int PREC, int LS, bool SB = true>
 __device__ __forceinline__ void mfma_bf16_ktile(f32x16 (&acc)[TM][TN], float (*A)[LS], float (*B)[LS], int a0,
                                                 int b0, int lane) {
   const int r = lane & 31, h = lane >> 5;
@@ -227,7 +227,7 @@ __device__ __forceinline__ void mfma_bf16_ktile(f32x16 (&acc)[TM][TN], float (*A
   }
   // every fragment read is issued before the first MFMA: the chain then waits on counted
   // lgkmcnt instead of re-reading into one register between MFMAs
-  __builtin_amdgcn_sched_barrier(0);
+  if (SB) __builtin_amdgcn_sched_barrier(0);
   if (PREC == 1) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -246,7 +246,10 @@ __device__ __forceinline__ void mfma_bf16_ktile(f32x16 (&acc)[TM][TN], float (*A
 
 // bf16x6: six products lo*hi + mid*mid + hi*lo + mid*hi + hi*mid + hi*hi (smallest first) of
 // three-way splits; the dropped terms are below 2^-24 of |a b| (fp32-like error)
-template <int TM, int TN, int LS>
+// SB: every fragment read is pinned ahead of the first MFMA.  Without it (the weight gradient's fused
+// stage, which places the reads itself with sched_group_barrier) the reads stand in the order the
+// products need them -- A0, every B, A1, ... -- so the first product waits only for its own six.
+template <int TM, int TN, int LS, bool SB = true>
 __device__ __forceinline__ void mfma_bf16x6_ktile(f32x16 (&acc)[TM][TN], float (*A)[LS], float (*B)[LS], int a0,
                                                   int b0, int lane) {
   const int r = lane & 31, h = lane >> 5;
@@ -257,15 +260,26 @@ __device__ __forceinline__ void mfma_bf16x6_ktile(f32x16 (&acc)[TM][TN], float (
     ah[i] = *reinterpret_cast<const bf16x8_t*>(p);
     am[i] = *reinterpret_cast<const bf16x8_t*>(p + 8);
     al[i] = *reinterpret_cast<const bf16x8_t*>(p + 16);
-  }
+    if (!SB && i == 0) {
 #pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const float* p = &B[b0 + j * 32 + r][4 * h];
-    bh[j] = *reinterpret_cast<const bf16x8_t*>(p);
-    bm[j] = *reinterpret_cast<const bf16x8_t*>(p + 8);
-    bl[j] = *reinterpret_cast<const bf16x8_t*>(p + 16);
+      for (int j = 0; j < TN; ++j) {
+        const float* q = &B[b0 + j * 32 + r][4 * h];
+        bh[j] = *reinterpret_cast<const bf16x8_t*>(q);
+        bm[j] = *reinterpret_cast<const bf16x8_t*>(q + 8);
+        bl[j] = *reinterpret_cast<const bf16x8_t*>(q + 16);
+      }
+    }
   }
-  __builtin_amdgcn_sched_barrier(0);
+  if (SB) {
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const float* p = &B[b0 + j * 32 + r][4 * h];
+      bh[j] = *reinterpret_cast<const bf16x8_t*>(p);
+      bm[j] = *reinterpret_cast<const bf16x8_t*>(p + 8);
+      bl[j] = *reinterpret_cast<const bf16x8_t*>(p + 16);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll

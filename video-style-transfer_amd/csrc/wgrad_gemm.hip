@@ -376,9 +376,41 @@ struct Wg2Params {
   int asplit, Ha;  // row-split A (vst_conv_wgrad_rowsplit): m = co*asplit + kh reads a[co][oy-kh][ox], a has Ha rows
 };
 
+template <int V>
+struct wg_ic {
+  static constexpr int value = V;
+};
+
+// Issue order of the fused stage of wgrad2_kernel's pipelined loop (one scheduling region: the
+// fragment reads and MFMAs of one k-tile, the split VALU and LDS writes of the next), from the tile's
+// constants.  An MFMA holds the SIMD's vector issue for 8 of its 32 cycles, so a few independent
+// single-issue VALU fit in every MFMA's shadow: per group one MFMA, one fragment read while any are
+// left (the first product's own reads lead; never more than two reads per gap), VPG split VALU and
+// the LDS writes spread evenly, two write slots behind the VALU that feed them.  Tiles with few MFMAs
+// per k-tile cannot hide all of their split: VPG stops at 5 and the rest follows the last MFMA.
+//   PAIRS: element pairs a thread splits per k-tile, WTASK: its LDS-write tasks (sections each)
+template <int PREC, int TM, int TN, int PAIRS, int WTASK>
+__device__ __forceinline__ void wg2_interleave() {
+  constexpr int NMF = (PREC == 3 ? 6 : (PREC == 1 ? 3 : 8)) * TM * TN;     // MFMAs per wave and k-tile
+  constexpr int SEC = PREC == 3 ? 3 : 2;                                    // LDS sections per row
+  constexpr int NRD = SEC * (TM + TN), RD0 = 2 * SEC;                       // fragment reads; the first product's
+  constexpr int NV = PAIRS * (PREC == 3 ? 11 : (PREC == 1 ? 6 : 0));        // split VALU (scalar subtractions)
+  constexpr int VPG = (NV + NMF - 1) / NMF < 5 ? (NV + NMF - 1) / NMF : 5;
+  constexpr int NW = SEC * WTASK, WLAG = 2 * ((NMF + NW - 1) / NW);
+  __builtin_amdgcn_sched_group_barrier(0x100, RD0, 0);
+#pragma unroll
+  for (int g = 0; g < NMF; ++g) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    if (RD0 + g < NRD) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    if (VPG > 0) __builtin_amdgcn_sched_group_barrier(0x002, VPG, 0);
+    const int h = g - WLAG;  // writes due by group h of an even spread
+    if (h >= 0 && (h + 1) * NW / NMF > h * NW / NMF) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+  }
+}
+
 // KD: k-tiles per LDS stage (one barrier per KD tiles); two for the single-product modes, whose
 // k loop does 4-6 MFMAs per wave and tile and is otherwise paced by the per-tile barrier
-// (one stage of loads in flight; the round-3 two-stage variant measured no gain and was removed)
+// (KD = 2: one stage of loads in flight; KD = 1: the pipelined loop below, two)
 template <int WM, int TM, int WN, int TN, int MINW, int PREC, int GMODE, int KD = 1, bool S1 = false>
 __global__ __launch_bounds__(WM * WN * 64, MINW) void wgrad2_kernel(Wg2Params P) {
   constexpr int NTH = WM * WN * 64;
@@ -396,6 +428,14 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void wgrad2_kernel(Wg2Params P)
   constexpr int B_TASKS = 2 * BN, B_IT = (B_TASKS + NTH - 1) / NTH;
   constexpr int OOR = 0x7ffffff0;
   static_assert(BK == 16, "16-pixel k-tiles");
+  // PIPE: the software-pipelined k loop (below), for the straight-line bf16x6 instantiations -- the
+  // mode whose three-way split is a third of the plain loop's time.  The rest keep the plain loop:
+  // the single-product modes (KD = 2) have a short last stage and next to no split; under f32 /
+  // bf16x3 the second register set costs the 32- / 64- / 128-row tiles a resident block per CU
+  // (bf16x6 loses none); and the stride-2 / nearest-x2 / row-split gathers (!S1) issue a path-
+  // dependent number of loads, so the compiler's wait before the split also covers loads of the
+  // tile just requested (measured: conv2 0.621 -> 0.637 ms, conv3 0.347 -> 0.352 ms pipelined).
+  constexpr bool PIPE = KD == 1 && PREC == 3 && S1;
 
   __shared__ __attribute__((aligned(16))) float As[2][KD][BM][LS];
   __shared__ __attribute__((aligned(16))) float Bs[2][KD][BN][LS];
@@ -418,8 +458,9 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void wgrad2_kernel(Wg2Params P)
   const long a_img = P.asplit ? (long)(P.M / P.asplit) * P.Ha * P.Wo : (long)P.M * HWo;
   const float* a_n = P.a + (long)n * a_img;
   const float* src_n = P.src + (long)n * P.Cs * plane;
-  const __amdgpu_buffer_rsrc_t asrd = uniform_rsrc(a_n, (uint32_t)(a_img * 4));
-  const __amdgpu_buffer_rsrc_t bsrd = uniform_rsrc(src_n, (uint32_t)((long)P.Cs * plane * 4));
+  const uint32_t a_bytes = (uint32_t)(a_img * 4), b_bytes = (uint32_t)((long)P.Cs * plane * 4);
+  const __amdgpu_buffer_rsrc_t asrd0 = uniform_rsrc(a_n, a_bytes);
+  const __amdgpu_buffer_rsrc_t bsrd0 = uniform_rsrc(src_n, b_bytes);
   const int Hv = S1 ? P.Hs : P.Hs * P.up, Wv = S1 ? P.Ws : P.Ws * P.up, sh = P.up - 1;
 
   // A tasks: (row, half) with 8 consecutive lanes on 8 consecutive rows of one half.  Row-split A:
@@ -473,8 +514,15 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void wgrad2_kernel(Wg2Params P)
   int t_oy = __builtin_amdgcn_readfirstlane(r_begin / P.Wo);
   int t_ox = __builtin_amdgcn_readfirstlane(r_begin - t_oy * P.Wo);
 
+  // PIPE: the loads run two tiles ahead of the MFMAs, unbranched.  A tile past the block's last one
+  // is loaded through zero-sized descriptors: every load of it is out of range, returns zeros and
+  // touches no memory (a prefetch under a branch would put the split + store back into a basic block
+  // of its own, behind the MFMAs).
   auto load_tile = [&](f32x4 (&ra)[A_IT][2], float (&rb)[B_IT][8], int t) {
     const int soff = __builtin_amdgcn_readfirstlane((r_begin + t * BK) * 4);
+    const bool live = !PIPE || t < ntiles;  // block-uniform
+    const __amdgpu_buffer_rsrc_t asrd = PIPE ? uniform_rsrc(a_n, live ? a_bytes : 0u) : asrd0;
+    const __amdgpu_buffer_rsrc_t bsrd = PIPE ? uniform_rsrc(src_n, live ? b_bytes : 0u) : bsrd0;
 #pragma unroll
     for (int i = 0; i < A_IT; ++i) {
       if (!S1 && P.asplit) {  // wave-uniform branch
@@ -504,8 +552,26 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void wgrad2_kernel(Wg2Params P)
       const int rowoff = b_cbase[i] + (S1 ? yv : yv >> sh) * P.Ws;
       const int xv0 = (t_ox + 8 * b_half[i]) * stride + b_kw[i] - P.pad;
       const int xv7 = xv0 + 7 * stride;
-      if (xv0 >= 0 && xv7 < Wv) {  // interior window: one base, immediate offsets
-        if (up == 2) {             // nearest x2: 8 virtual columns over 4-5 source columns
+      const bool inter = xv0 >= 0 && xv7 < Wv;
+      if constexpr (S1 && PIPE) {
+        // the interior window's two 16-byte loads are issued by every lane (out of range on a border
+        // window, whose lanes then load per element below): the count of vector loads behind the
+        // previous tile's is then the same on every path a wave without border lanes can take, and
+        // the wait the compiler puts before that tile's split is exactly vmcnt(loads of this tile)
+        // -- with the pair under the branch it counted the path that skips both forms and waited
+        // for this tile's first loads
+        const int vo = (ok && inter) ? (rowoff + xv0) * 4 : OOR;
+        const f32x4 a0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(bsrd, vo, 0, 0));
+        const f32x4 a1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(bsrd, vo + 16, 0, 0));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          rb[i][e] = a0[e];
+          rb[i][4 + e] = a1[e];
+        }
+      }
+      if (inter) {  // interior window: one base, immediate offsets
+        if constexpr (S1 && PIPE) {
+        } else if (up == 2) {  // nearest x2: 8 virtual columns over 4-5 source columns
           const int vo = ok ? (rowoff + (xv0 >> 1)) * 4 : OOR;
           float s[5];
 #pragma unroll
@@ -543,7 +609,10 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void wgrad2_kernel(Wg2Params P)
             oke = oke && xv >= 0 && xv < Wv;
           }
           const int vo = oke ? (rowoff + (S1 ? xv : xv >> sh)) * 4 : OOR;
-          rb[i][e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(bsrd, vo, 0, 0));
+          const uint32_t v = __builtin_amdgcn_raw_buffer_load_b32(bsrd, vo, 0, 0);
+          // (S1 && PIPE: OR-ed onto the zero bits the out-of-range pair above returned on this lane --
+          // the pair is then live on both paths and stays in front of the branch)
+          rb[i][e] = __uint_as_float((S1 && PIPE) ? (v | __float_as_uint(rb[i][e])) : v);
         }
       }
     }
@@ -617,11 +686,13 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void wgrad2_kernel(Wg2Params P)
   };
 
   const int lo = lane & 31, hi = lane >> 5;
-  auto mfma_tile = [&](int buf, int d) {
+  // (SB: the fragment reads pinned ahead of the MFMAs, vst_common.h; the fused stage places them itself)
+  auto mfma_tile = [&](int buf, int d, auto sb) {
+    constexpr bool SB = decltype(sb)::value != 0;
     if constexpr (PREC == 3) {
-      mfma_bf16x6_ktile<TM, TN, LS>(acc, As[buf][d], Bs[buf][d], wm * TM * 32, wn * TN * 32, lane);
+      mfma_bf16x6_ktile<TM, TN, LS, SB>(acc, As[buf][d], Bs[buf][d], wm * TM * 32, wn * TN * 32, lane);
     } else if constexpr (PREC != 0) {
-      mfma_bf16_ktile<TM, TN, PREC, LS>(acc, As[buf][d], Bs[buf][d], wm * TM * 32, wn * TN * 32, lane);
+      mfma_bf16_ktile<TM, TN, PREC, LS, SB>(acc, As[buf][d], Bs[buf][d], wm * TM * 32, wn * TN * 32, lane);
     } else {
       f32x4 a[TM][2], b[TN][2];
 #pragma unroll
@@ -667,18 +738,55 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void wgrad2_kernel(Wg2Params P)
   auto compute_stage = [&](int st) {
 #pragma unroll
     for (int d = 0; d < KD; ++d)
-      if (d == 0 || st * KD + d < ntiles) mfma_tile(st & 1, d);
+      if (d == 0 || st * KD + d < ntiles) mfma_tile(st & 1, d, wg_ic<1>{});
   };
-  if (ntiles > 0) {
-    load_stage(0);
-    store_stage(0, 0);
-  }
-  __syncthreads();
-  for (int st = 0; st < nst; ++st) {
-    if (st + 1 < nst) load_stage(st + 1);
-    compute_stage(st);
-    if (st + 1 < nst) store_stage((st & 1) ^ 1, st + 1);
+  if constexpr (PIPE) {
+    // Software-pipelined loop, one basic block per stage.  Stage st issues the global loads of tile
+    // st + 2 into the register set tile st + 1 is not held in (two sets, the loop unrolled by two),
+    // then runs the MFMAs of tile st (LDS buffer st & 1) interleaved with the split and the LDS writes
+    // of tile st + 1 (loaded one stage earlier: its wait is vmcnt(loads just issued), never 0) into the
+    // other buffer, then one barrier.  The same k-tiles in the same order, the same MFMA sequence per
+    // accumulator and the same split arithmetic as the plain loop: only the issue order moves.
+    // Past the block's last tile the loads return zeros (load_tile) and the store goes to the buffer
+    // nobody reads, so no stage carries a branch and a block without tiles still writes its zero slab.
+    f32x4 RA2[A_IT][2];
+    float RB2[B_IT][8];
+    load_tile(RA[0], RB[0], 0);
+    advance();
+    store_tile(0, 0, RA[0], RB[0]);
+    load_tile(RA2, RB2, 1);
+    advance();
     __syncthreads();
+    auto stage = [&](auto bufc, int st, const f32x4 (&ras)[A_IT][2], const float (&rbs)[B_IT][8],
+                     f32x4 (&ral)[A_IT][2], float (&rbl)[B_IT][8]) {
+      constexpr int buf = decltype(bufc)::value;
+      load_tile(ral, rbl, st + 2);
+      advance();
+      __builtin_amdgcn_sched_barrier(0);  // the loads stay ahead of the fused stage
+      mfma_tile(buf, 0, wg_ic<0>{});
+      store_tile(buf ^ 1, 0, ras, rbs);
+      wg2_interleave<PREC, TM, TN, (A_IT * AQ + B_IT * 8) / 2, A_IT + B_IT>();
+      __syncthreads();
+    };
+    // (pairs in the loop, an odd last stage after it: no branch around a stage inside the loop)
+    int st = 0;
+    for (; st + 1 < nst; st += 2) {
+      stage(wg_ic<0>{}, st, RA2, RB2, RA[0], RB[0]);
+      stage(wg_ic<1>{}, st + 1, RA[0], RB[0], RA2, RB2);
+    }
+    if (st < nst) stage(wg_ic<0>{}, st, RA2, RB2, RA[0], RB[0]);
+  } else {
+    if (ntiles > 0) {
+      load_stage(0);
+      store_stage(0, 0);
+    }
+    __syncthreads();
+    for (int st = 0; st < nst; ++st) {
+      if (st + 1 < nst) load_stage(st + 1);
+      compute_stage(st);
+      if (st + 1 < nst) store_stage((st & 1) ^ 1, st + 1);
+      __syncthreads();
+    }
   }
 
   float* slab = P.slab + (long)bz * P.Mpad * P.Jpad;
