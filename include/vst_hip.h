@@ -135,6 +135,16 @@ int vst_fold_border(const float* border, const float* mask, float* dx, long NC, 
  * Cin even, W % 4 == 0, W >= 8; mask NULL or dx-shaped. */
 int vst_conv_dgrad_thin(const float* dy, const float* w, const float* mask, float* dx, float* border, int N, int Cout,
                         int Cin, int H, int W, int reflect, void* stream);
+/* forward of the same conv (3x3 stride 1 pad 1, reflect != 0: reflection pad, else zero pad; 1..4 output
+ * channels), in exact fp32 on the VALU (no MFMA, no GEMM mode): out ([N][Cout][H][W] fp32, may be NULL)
+ * = conv(x, w) + bias (bias may be NULL); frames ([N][H][W][3] uint8, may be NULL, needs Cout == 3)
+ * receives clamp(out, 0, 255) truncated to uint8 in HWC order (swap_rb: BGR) in the same pass, byte for
+ * byte what vst_tensor_to_frames makes of `out`.  At least one of out / frames.  w: [Cout][Cin][3][3];
+ * any Cin >= 1, H >= 2, W % 4 == 0, W >= 8; x / out 16-byte, frames 4-byte aligned.  An output element
+ * depends only on its own inputs (fixed summation order, csrc/thin.hip): an image in a batch is bitwise
+ * the image alone. */
+int vst_conv_thin_fwd(const float* x, const float* w, const float* bias, float* out, void* frames, int N, int Cin,
+                      int H, int W, int Cout, int reflect, int swap_rb, void* stream);
 /* Thin-channel convolutions (RC/network.py:155 conv1 = ConvLayer(3, 48, 9), :169 deconv3 =
  * ConvTanh(48, 3, 9) backward, VGG conv1_1): a tensor with C*K <= Cu channels is kw-unfolded,
  *   out[n][c*K + kw][y][v] = src[n][c][y][v + sgn*kw + off]  (reflect or zero outside; zero channels

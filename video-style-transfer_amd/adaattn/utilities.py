@@ -5,4 +5,4 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from vst.adaattn.utilities import feature_down_sample, flow_warp_mask, vgg_normalize, warp  # noqa: E402,F401
+from vst.adaattn.utilities import cv2_to_tensor, feature_down_sample, flow_warp_mask, vgg_normalize, warp  # noqa: E402,F401

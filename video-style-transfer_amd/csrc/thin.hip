@@ -2,7 +2,8 @@
 // AA/network.py:99): weight and data gradients in exact fp32 on the VALU.  As GEMMs their M (3, or 9
 // row-split rows) fills a tenth of a 32-row MFMA tile while the operand gathers and the 2 GB-class
 // activation read / write stay whole (config 5: 2.3 ms each); here each source / output row is moved
-// once, with 16-byte accesses.
+// once, with 16-byte accesses.  The forward (inference only: the training forward stays on the GEMM)
+// is the third kernel below; it can write the uint8 frame in the same pass.
 //
 // Built with -fno-slp-vectorize (Makefile): the packed pairs below are written out explicitly
 // (v_pk_fma_f32 over column pairs); the SLP vectorizer paired the scalar weight FMAs of the data
@@ -454,6 +455,195 @@ __global__ void thin_dgrad_ring_kernel(const float* __restrict__ dy, const float
 }
 
 
+// ---------------------------------------------------------------------------------------------
+// Forward of a 3x3 stride-1 pad-1 conv with at most 4 output channels (the AdaAttN decoder's last
+// conv 64 -> 3, AA/network.py:99, which at inference produces the frame), in exact fp32 on the VALU:
+//   Y[co][y][x] = b[co] + sum_{ci,kh,kw} W[co][ci][kh][kw] * Xpad[ci][y + kh][x + kw]
+// As a GEMM its M is 3: a 32-row MFMA tile wastes 90 % of its products and every source element is
+// gathered once per tap.  Here a lane owns 4 consecutive columns of R (2 or 4) consecutive rows of
+// ALL output channels, and the four waves of a block own the same pixels and a quarter of the input
+// channels each (wave p: ci = p, p + 4, p + 8, ...).  Per channel a lane loads the R + 2 source rows
+// (16 B + the two 4-byte neighbour columns each; the halo rows are shared with the row tile above /
+// below through L2, so an element comes from HBM about once) and the channel's CO x 9 weights
+// through scalar loads (the address is wave-uniform); the next channel's rows and weights are loaded
+// before this channel's FMAs (packed pairs over columns).  The four partial sums meet in LDS.
+//
+// Accumulation order (fixed; independent of N, the launch geometry, R and the element's place in a
+// tile, so an image in a batch is bitwise the image alone):
+//   S_p = fma chain from 0 over ci = p, p + 4, ... ascending, then kh = 0..2, then kw = 0..2
+//   Y   = ((S_0 + S_1) + (S_2 + S_3)) + b
+// (a wave without channels contributes S_p = 0).  frames (CO == 3): clamp(Y, 0, 255) truncated to
+// uint8, HWC, written in the same pass with the arithmetic of vst_tensor_to_frames (frames.hip).
+struct ThinFwParams {
+  const float* x;     // [N][Cin][H][W]
+  const float* w;     // [CO][Cin][3][3]
+  const float* bias;  // [CO] or null
+  float* out;         // [N][CO][H][W] or null
+  uint32_t* frames;   // [N][H][W][3] uint8 or null
+  int Cin, H, W;
+  int tcb, rpar, ncolb, nrowb, swap;
+};
+constexpr int THIN_FW_PARTS = 4;  // channel partials = waves per block
+
+template <int CO, int R, bool REFLECT>
+__global__ __launch_bounds__(256) void thin_fwd_kernel(ThinFwParams P) {
+  constexpr int OOR = 0x7ffffff0, SR = R + 2;
+  const int wk = xcd_remap(blockIdx.x, gridDim.x);
+  const int colb = __builtin_amdgcn_readfirstlane(wk % P.ncolb);
+  int rest = __builtin_amdgcn_readfirstlane(wk / P.ncolb);
+  const int rowb = __builtin_amdgcn_readfirstlane(rest % P.nrowb);
+  const int n = __builtin_amdgcn_readfirstlane(rest / P.nrowb);
+  const int H = P.H, W = P.W, Cin = P.Cin;
+  const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int rl = lane / P.tcb, q = lane - rl * P.tcb;
+  const int px0 = 4 * (colb * P.tcb + q);
+  const int y0 = (rowb * P.rpar + rl) * R;
+  const bool act = rl < P.rpar && px0 < W && y0 < H;
+  const long plane = (long)H * W;
+  const int pstride = (int)(plane * 4);
+  const __amdgpu_buffer_rsrc_t xr = uniform_rsrc(P.x + (long)n * Cin * plane, (uint32_t)(Cin * plane * 4));
+  // byte offsets of the 16-byte body and the two neighbour columns of source rows y0 - 1 .. y0 + R
+  int cl = px0 - 1, cr = px0 + 4;
+  if (REFLECT) {
+    cl = cl < 0 ? 1 : cl;
+    cr = cr >= W ? W - 2 : cr;
+  } else {
+    cl = cl < 0 ? -1 : cl;
+    cr = cr >= W ? -1 : cr;
+  }
+  int vm[SR], vl[SR], vr[SR];
+#pragma unroll
+  for (int s = 0; s < SR; ++s) {
+    const int r = y0 - 1 + s;
+    int rr = r;
+    bool ok = act;
+    if (REFLECT) {
+      ok = ok && r <= H;  // (r >= -1 always; rows past H feed only output rows past the image)
+      rr = rr < 0 ? 1 : (rr >= H ? 2 * H - 2 - rr : rr);
+    } else {
+      ok = ok && r >= 0 && r < H;
+    }
+    const int rb = rr * W * 4;
+    vm[s] = ok ? rb + px0 * 4 : OOR;
+    vl[s] = ok && cl >= 0 ? rb + cl * 4 : OOR;
+    vr[s] = ok && cr >= 0 ? rb + cr * 4 : OOR;
+  }
+
+  f32x2 acc[CO][R][2];  // {columns 0, 1}, {columns 2, 3} of an output row
+#pragma unroll
+  for (int co = 0; co < CO; ++co)
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[co][r][0] = acc[co][r][1] = f32x2{0.f, 0.f};
+  float X[2][SR][6];   // the source rows of the current and the prefetched channel
+  float Wt[2][CO][9];  // their weights (wave-uniform: scalar registers)
+  auto load_x = [&](int ci, float (&xv)[SR][6]) {
+    const int so = ci * pstride;
+#pragma unroll
+    for (int s = 0; s < SR; ++s) {
+      const f32x4 m = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, vm[s], so, 0));
+      xv[s][0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xr, vl[s], so, 0));
+      xv[s][1] = m[0];
+      xv[s][2] = m[1];
+      xv[s][3] = m[2];
+      xv[s][4] = m[3];
+      xv[s][5] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xr, vr[s], so, 0));
+    }
+  };
+  auto load_w = [&](int ci, float (&wv)[CO][9]) {
+#pragma unroll
+    for (int co = 0; co < CO; ++co)
+#pragma unroll
+      for (int k = 0; k < 9; ++k) wv[co][k] = P.w[((long)co * Cin + ci) * 9 + k];
+  };
+  const int nch = wave < Cin ? (Cin - wave + THIN_FW_PARTS - 1) / THIN_FW_PARTS : 0;
+  float bv[CO];  // (read ahead of every store: scalar loads)
+#pragma unroll
+  for (int co = 0; co < CO; ++co) bv[co] = P.bias ? P.bias[co] : 0.f;
+  auto step = [&](auto pc, int i) {
+    constexpr int p = decltype(pc)::value;
+    const int ci = wave + THIN_FW_PARTS * i;
+    if (i + 1 < nch) {
+      load_x(ci + THIN_FW_PARTS, X[p ^ 1]);
+      load_w(ci + THIN_FW_PARTS, Wt[p ^ 1]);
+    }
+    const float(&wv)[CO][9] = Wt[p];
+#pragma unroll
+    for (int s = 0; s < SR; ++s) {  // source row y0 - 1 + s meets output row s - kh through tap row kh
+      const float(&xv)[6] = X[p][s];
+      f32x2 xp[5];  // source pairs {x_c, x_c+1}, c = j + kw
+#pragma unroll
+      for (int c = 0; c < 5; ++c) xp[c] = f32x2{xv[c], xv[c + 1]};
+#pragma unroll
+      for (int kh = 0; kh < 3; ++kh) {
+        const int o = s - kh;
+        if (o < 0 || o >= R) continue;
+#pragma unroll
+        for (int co = 0; co < CO; ++co)
+#pragma unroll
+          for (int kw = 0; kw < 3; ++kw) {
+            const f32x2 wp = {wv[co][kh * 3 + kw], wv[co][kh * 3 + kw]};
+            acc[co][o][0] = __builtin_elementwise_fma(wp, xp[kw], acc[co][o][0]);
+            acc[co][o][1] = __builtin_elementwise_fma(wp, xp[kw + 2], acc[co][o][1]);
+          }
+      }
+    }
+  };
+  if (nch > 0) {
+    load_x(wave, X[0]);
+    load_w(wave, Wt[0]);
+  }
+  for (int i = 0; i < nch; i += 2) {
+    step(std::integral_constant<int, 0>{}, i);
+    if (i + 1 < nch) step(std::integral_constant<int, 1>{}, i + 1);
+  }
+
+  // the four channel partials of a lane's CO x R row quads meet in LDS; wave p finishes rows p, p + 4, ...
+  __shared__ f32x4 red[THIN_FW_PARTS][CO * R][64];
+#pragma unroll
+  for (int co = 0; co < CO; ++co)
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      red[wave][co * R + r][lane] = f32x4{acc[co][r][0][0], acc[co][r][0][1], acc[co][r][1][0], acc[co][r][1][1]};
+  __syncthreads();
+  for (int r = wave; r < R; r += THIN_FW_PARTS) {
+    const int y = y0 + r;
+    if (!(act && y < H)) continue;
+    f32x4 v[CO];
+#pragma unroll
+    for (int co = 0; co < CO; ++co) {
+      const int k = co * R + r;
+      v[co] = (red[0][k][lane] + red[1][k][lane]) + (red[2][k][lane] + red[3][k][lane]);
+      if (P.bias) v[co] += bv[co];
+      if (P.out) *reinterpret_cast<f32x4*>(P.out + (((long)n * CO + co) * H + y) * W + px0) = v[co];
+    }
+    if constexpr (CO == 3) {
+      if (P.frames) {
+        uint32_t b[12];
+#pragma unroll
+        for (int co = 0; co < 3; ++co)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float f = v[co][j];
+            b[3 * j + co] = (uint32_t)(int)(f < 0.f ? 0.f : (f > 255.f ? 255.f : f));
+          }
+        if (P.swap) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const uint32_t t0 = b[3 * j];
+            b[3 * j] = b[3 * j + 2];
+            b[3 * j + 2] = t0;
+          }
+        }
+        uint32_t* d = P.frames + (((long)n * H + y) * W + px0) * 3 / 4;
+        d[0] = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+        d[1] = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
+        d[2] = b[8] | (b[9] << 8) | (b[10] << 16) | (b[11] << 24);
+      }
+    }
+  }
+}
+
+
 }  // namespace
 
 bool vst_thin_wgrad_ok(int Cout, int Cin, int Hs, int Ws, int Ho, int Wo, int KH, int KW, int gmode, int stride,
@@ -513,6 +703,53 @@ int vst_conv_dgrad_thin(const float* dy, const float* w, const float* mask, floa
     const int rc = vst_launch_status();
     if (rc) return rc;
     return vst_fold_border(border, mask, dx, (long)N * Cin, H, W, 1, stream);
+  }
+  return vst_launch_status();
+}
+
+int vst_conv_thin_fwd(const float* x, const float* w, const float* bias, float* out, void* frames, int N, int Cin,
+                      int H, int W, int Cout, int reflect, int swap_rb, void* stream) {
+  VST_CHECK_ARG(x && w && (out || frames) && N > 0 && Cin >= 1 && Cout >= 1 && Cout <= 4 && H >= 2 && W >= 8 &&
+                W % 4 == 0 && (!frames || Cout == 3));
+  // 16-byte row accesses, dword frame stores, 32-bit byte offsets inside one image's planes
+  VST_CHECK_ARG((uintptr_t)x % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)frames % 4 == 0 &&
+                (long)Cin * H * W * 4 <= 0x7ffffff0L && (long)N * H * W < 0x7fffffffL);
+  const int quads = W / 4;
+  ThinFwParams P;
+  P.x = x;
+  P.w = w;
+  P.bias = bias;
+  P.out = out;
+  P.frames = (uint32_t*)frames;
+  P.Cin = Cin;
+  P.H = H;
+  P.W = W;
+  P.swap = swap_rb;
+  // a wave covers up to 64 column quads of rpar row tiles; 4-row tiles once they fill the device twice
+  P.tcb = quads >= 64 ? 64 : quads;
+  P.ncolb = (quads + P.tcb - 1) / P.tcb;
+  P.rpar = 64 / P.tcb;
+  const long b4 = (long)N * P.ncolb * ((H + 4 * P.rpar - 1) / (4 * P.rpar));
+  const int R = b4 >= 512 ? 4 : 2;
+  P.nrowb = (H + R * P.rpar - 1) / (R * P.rpar);
+  const int g = N * P.ncolb * P.nrowb;
+  hipStream_t st = (hipStream_t)stream;
+  switch (Cout) {
+#define VST_THIN_FW(C)                                                                \
+  case C:                                                                             \
+    if (R == 4) {                                                                     \
+      if (reflect) thin_fwd_kernel<C, 4, true><<<g, 256, 0, st>>>(P);                 \
+      else thin_fwd_kernel<C, 4, false><<<g, 256, 0, st>>>(P);                        \
+    } else {                                                                          \
+      if (reflect) thin_fwd_kernel<C, 2, true><<<g, 256, 0, st>>>(P);                 \
+      else thin_fwd_kernel<C, 2, false><<<g, 256, 0, st>>>(P);                        \
+    }                                                                                 \
+    break;
+    VST_THIN_FW(1)
+    VST_THIN_FW(2)
+    VST_THIN_FW(3)
+    VST_THIN_FW(4)
+#undef VST_THIN_FW
   }
   return vst_launch_status();
 }

@@ -169,6 +169,38 @@ def _softmax_rows_per_block(N, Nc, Ns, budget=None):
     return max(32, rows // 32 * 32)
 
 
+def square_concat(V):
+    """VV2 = [V; V^2]  [N][2dv][Ns] (the style side of the softmax forward: with K, all it needs)."""
+    N, dv = V.shape[:2]
+    Ns = V[0, 0].numel()
+    VV2 = _empty((N, 2 * dv, Ns), V)
+    lib.vst_square_concat(ptr(V), ptr(VV2), N, dv * Ns, stream())
+    return VV2
+
+
+def softmax_moments(Qm, Km, VV2, block_rows=None):
+    """[M; E2] = VV2 softmax_rows(Q^T K)^T  [N][2dv][Nc] in blocks of query rows (the content side of
+    the softmax forward, shared by AdaAttnFn.forward and the inference path).  Returns (MV, A, C):
+    A is the attention matrix when one block held it all (else None), C the rows per block."""
+    N, d, Nc = Qm.shape
+    Ns = Km.shape[2]
+    role = "attn_" + SOFTMAX
+    C = _softmax_rows_per_block(N, Nc, Ns) if block_rows is None else min(int(block_rows), Nc)
+    A = None
+    if C == Nc:
+        S = bmm_at_b(Qm, Nc, d, False, Km, Ns, role=role)  # [N][Nc][Ns]
+        A, _ = attention_rows(S, SOFTMAX)
+        del S
+        MV = gemm_abt(VV2, A, role=role)
+    else:
+        MV = _empty((N, VV2.shape[1], Nc), VV2)
+        for c0 in range(0, Nc, C):
+            Cb = min(C, Nc - c0)
+            Ab = _softmax_block(Qm, Km, c0, Cb, role)
+            copy_cols(gemm_abt(VV2, Ab, role=role), 0, Cb, dst=MV, d0=c0)
+    return MV, A, C
+
+
 class AdaAttnFn(Function):
     """out = sqrt(clamp(A V^2 - (A V)^2, 1e-6)) * cn + A V  with A = activation(Q^T K)
     (AA/network.py:191-220 after the 1x1 convs).  Gradients for Q, K, V.  Softmax: query-row blocks
@@ -187,8 +219,7 @@ class AdaAttnFn(Function):
         Qm, Km = Q.view(N, d, Nc), K.view(N, d, Ns)
         role = "attn_" + activation
         qn = kn = S = rowsum = None
-        VV2 = _empty((N, 2 * dv, Ns), V)
-        lib.vst_square_concat(ptr(V), ptr(VV2), N, dv * Ns, stream())
+        VV2 = square_concat(V)
         if activation == COSINE:
             qn, kn = channel_norm(Qm), channel_norm(Km)
             ks = _vec((N, Ns), Q)
@@ -201,19 +232,7 @@ class AdaAttnFn(Function):
             MV = gemm_abt(VV2, A, role=role)  # [N][2dv][Nc]
             C = Nc
         elif activation == SOFTMAX:
-            C = _softmax_rows_per_block(N, Nc, Ns) if block_rows is None else min(int(block_rows), Nc)
-            A = None
-            if C == Nc:
-                S = bmm_at_b(Qm, Nc, d, False, Km, Ns, role=role)  # [N][Nc][Ns]
-                A, _ = attention_rows(S, activation)
-                del S
-                MV = gemm_abt(VV2, A, role=role)
-            else:
-                MV = _empty((N, 2 * dv, Nc), V)
-                for c0 in range(0, Nc, C):
-                    Cb = min(C, Nc - c0)
-                    Ab = _softmax_block(Qm, Km, c0, Cb, role)
-                    copy_cols(gemm_abt(VV2, Ab, role=role), 0, Cb, dst=MV, d0=c0)
+            MV, A, C = softmax_moments(Qm, Km, VV2, block_rows)
         else:
             raise ValueError(f"Unknown activation function: {activation}")
         out = _empty((N, dv, h, w), V)
@@ -374,6 +393,51 @@ def _recip(x):
     return y
 
 
+# The linear form's forward in three parts, shared by LinearCosineAttnFn.forward and the inference
+# path (inference.py), which runs the style part once per style and keeps only G, ksum, us and Ns.
+def cosine_query_side(Q):
+    """||q||, 1 / ||q|| [Nq][Nc] and qh = q / ||q|| [Nq][d][Nc]."""
+    Nq, d = Q.shape[:2]
+    Qm = Q.view(Nq, d, -1)
+    qn = channel_norm(Qm)
+    qs = _recip(qn)
+    return qn, qs, _normalized(Qm, qs)
+
+
+def cosine_style_side(K, V):
+    """Everything the moments read from the style: kh [Nk][d][Ns], 1 / ||k||, U = [V; V^2],
+    G = Kh U^T [Nk][d][2dv], ksum = sum_j kh_j [Nk][d], us = sum_j U_j [Nk][2dv]."""
+    Nk, d = K.shape[:2]
+    dv = V.shape[1]
+    Km = K.view(Nk, d, -1)
+    Ns = Km.shape[2]
+    role = "attn_" + COSINE
+    ks = _recip(channel_norm(Km))
+    Kh = _normalized(Km, ks)
+    U = _empty((Nk, 2 * dv, Ns), V)
+    lib.vst_square_concat(ptr(V), ptr(U), Nk, dv * Ns, stream())
+    G = gemm_abt(Kh, U, role=role)
+    return Kh, ks, U, G, plane_dot(Kh), plane_dot(U)
+
+
+def cosine_content_side(Q, qn, Qh, cn, G, ksum, us, Ns):
+    """out = sqrt(clamp(E2 - M^2, 1e-6)) * cn + M with [M; E2] = (G^T qh + us) / rs; G / ksum / us of
+    Nk styles are repeated over the Nq = r Nk queries.  Returns out and what the backward keeps."""
+    Nq, d, h, w = Q.shape
+    dv = cn.shape[1]
+    Nc = h * w
+    r = Nq // G.shape[0]
+    Gr, ksr, usr = _repeat(G, r), _repeat(ksum, r), _repeat(us, r)
+    qk = channel_dot(Q.view(Nq, d, Nc), v=ksr)          # q . ksum  [Nq][Nc]
+    rinv = _empty(qk.shape, qk)
+    lib.vst_attn_fwd_rows(ptr(qk), ptr(qn), ptr(_empty(qk.shape, qk)), ptr(rinv), qk.numel(), Ns,
+                          stream())                     # 1 / rs = 1 / (q . ksum / ||q|| + Ns)
+    MV = attn_gemm(Gr, 2 * dv, d, Qh, Nc, rb=None, cg=rinv, ra=usr, role="attn_" + COSINE)  # (G^T qh + us) / rs
+    out = _empty((Nq, dv, h, w), cn)
+    lib.vst_adaattn_out(ptr(MV), ptr(cn), ptr(out), Nq, dv * Nc, stream())
+    return out, MV, rinv, Gr, ksr
+
+
 class LinearCosineAttnFn(Function):
     """out = sqrt(clamp(E2 - M^2, 1e-6)) * cn + M with [M; E2] the cosine-attention moments in
     linear form (see above); gradients for Q, K, V."""
@@ -387,24 +451,9 @@ class LinearCosineAttnFn(Function):
         if (K.shape[1] != d or V.shape != (Nk, dv, hs, ws) or cn.shape != (Nq, dv, h, w) or Nq % Nk):
             raise VstError(f"adaattn: Q{tuple(Q.shape)} K{tuple(K.shape)} V{tuple(V.shape)} c{tuple(cn.shape)}")
         Q, K, V, cn = (ops._check(t, "adaattn operand", 4) for t in (Q, K, V, cn))
-        r = Nq // Nk
-        role = "attn_" + COSINE
-        Qm, Km = Q.view(Nq, d, Nc), K.view(Nk, d, Ns)
-        qn = channel_norm(Qm)
-        qs, ks = _recip(qn), _recip(channel_norm(Km))
-        Qh, Kh = _normalized(Qm, qs), _normalized(Km, ks)
-        U = _empty((Nk, 2 * dv, Ns), V)
-        lib.vst_square_concat(ptr(V), ptr(U), Nk, dv * Ns, stream())
-        G = gemm_abt(Kh, U, role=role)                       # [Nk][d][2dv]
-        ksum, us = plane_dot(Kh), plane_dot(U)              # [Nk][d], [Nk][2dv]
-        Gr, ksr, usr = _repeat(G, r), _repeat(ksum, r), _repeat(us, r)
-        qk = channel_dot(Qm, v=ksr)                         # q . ksum  [Nq][Nc]
-        rinv = _empty(qk.shape, qk)
-        lib.vst_attn_fwd_rows(ptr(qk), ptr(qn), ptr(_empty(qk.shape, qk)), ptr(rinv), qk.numel(), Ns,
-                              stream())                     # 1 / rs = 1 / (q . ksum / ||q|| + Ns)
-        MV = attn_gemm(Gr, 2 * dv, d, Qh, Nc, rb=None, cg=rinv, ra=usr, role=role)  # (G^T qh + us) / rs
-        out = _empty((Nq, dv, h, w), V)
-        lib.vst_adaattn_out(ptr(MV), ptr(cn), ptr(out), Nq, dv * Nc, stream())
+        qn, qs, Qh = cosine_query_side(Q)
+        Kh, ks, U, G, ksum, us = cosine_style_side(K, V)
+        out, MV, rinv, Gr, ksr = cosine_content_side(Q, qn, Qh, cn, G, ksum, us, Ns)
         ctx.dims = (Nq, Nk, d, dv, Nc, Ns, (h, w), (hs, ws))
         if any(ctx.needs_input_grad[:3]):
             ctx.save_for_backward(V, cn, Qh, Kh, qs, ks, U, Gr, ksr, MV, rinv)

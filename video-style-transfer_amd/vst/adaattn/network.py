@@ -106,6 +106,11 @@ class Decoder(nn.Module):
             return self._forward(x5, x4, x3)
 
     def _forward(self, x5, x4, x3):
+        return self.conv8.run(self.trunk(x5, x4, x3), act=None, mask_dx=True)
+
+    def trunk(self, x5, x4, x3):
+        """Everything up to conv7's output (the 64-channel input of the last conv): the training
+        forward and the inference path (inference.py, which runs conv8 on the thin forward kernel)."""
         # a ConvReLU whose output only feeds the next conv leaves its ReLU backward to that conv's
         # data gradient (premasked -> mask_dx: the mask is applied in the dgrad epilogue and border
         # fold); one whose output feeds an upsample leaves it to the upsample's adjoint (relu_mask)
@@ -121,8 +126,7 @@ class Decoder(nn.Module):
         x = ops.upsample2x(run(self.conv4, x, mask_dx=True, premasked=True), relu_mask=True)
         x = run(self.conv5, x, premasked=True)
         x = ops.upsample2x(run(self.conv6, x, mask_dx=True, premasked=True), relu_mask=True)
-        x = run(self.conv7, x, premasked=True)
-        return run(self.conv8, x, mask_dx=True)
+        return run(self.conv7, x, premasked=True)
 
 
 class Softmax(nn.Module):
@@ -183,11 +187,19 @@ class AdaAttN(nn.Module):
             return self._forward(c_x, s_x, c_1x, s_1x)
 
     def _forward(self, c_x, s_x, c_1x, s_1x):
-        with ops.gemm_scope("attn"):  # policy key "stylizer.attn.<role>" (fp16 policy: bf16x3 here)
-            Q = ops.conv2d(instance_norm_plain(c_1x), self.f.weight, self.f.bias)
-            K = ops.conv2d(instance_norm_plain(s_1x), self.g.weight, self.g.bias)
-            V = ops.conv2d(s_x, self.h.weight, self.h.bias)
+        Q = self.query(c_1x)
+        K, V = self.key_value(s_x, s_1x)
         return adaattn(Q, K, V, instance_norm_plain(c_x), self.activation.kind)
+
+    # the two sides of the projections (the inference path runs key_value once per style)
+    def query(self, c_1x):
+        with ops.gemm_scope("attn"):  # policy key "stylizer.attn.<role>" (fp16 policy: bf16x3 here)
+            return ops.conv2d(instance_norm_plain(c_1x), self.f.weight, self.f.bias)
+
+    def key_value(self, s_x, s_1x):
+        with ops.gemm_scope("attn"):
+            K = ops.conv2d(instance_norm_plain(s_1x), self.g.weight, self.g.bias)
+            return K, ops.conv2d(s_x, self.h.weight, self.h.bias)
 
 
 class StylizingNetwork(nn.Module):

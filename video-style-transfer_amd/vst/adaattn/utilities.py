@@ -1,4 +1,5 @@
 """Drop-in for the AdaAttN path's helpers in AA/utilities.py on HIP kernels."""
+import numpy as np
 import torch
 
 from .. import ops
@@ -9,6 +10,20 @@ from ..reconet.utilities import flow_warp_mask, warp  # noqa: F401  (AA/utilitie
 def vgg_normalize(batch):
     """AA/utilities.py:79-85 (out of place): (batch/255 - mean)/std, differentiable."""
     return ops.VggNormalizeFn.apply(batch.float() if batch.dtype != torch.float32 else batch)
+
+
+def cv2_to_tensor(img, resize=None, device="cuda"):
+    """AA/utilities.py:46-55: cv2 BGR uint8 frame -> (3,H,W) fp32 RGB in [0,255].  The channel swap
+    and ToTensor * 255 run in the HIP frame kernel on `device` (the reference returns a CPU tensor
+    that callers `.to(device)`); resize = (width, height) is cv2.resize(INTER_AREA) on the host as in
+    the reference (per channel, so it commutes with the swap) and needs cv2 unless the frame already
+    has that size."""
+    from ..video_io import host_frame  # noqa: PLC0415
+
+    img = np.asarray(img)
+    hw = img.shape[:2] if resize is None else (resize[1], resize[0])
+    f = torch.from_numpy(host_frame(img, hw, "INTER_AREA")).to(device)
+    return ops.frames_to_tensor(f.unsqueeze(0), bgr=True)[0]
 
 
 class _FeatureDownSample(torch.autograd.Function):

@@ -460,6 +460,34 @@ def conv_dgrad_thin(gz, w, x_shape, reflect, dmask=None):
     return dx
 
 
+def conv_thin_fwd(x, w, b=None, reflect=True, out=None, frames=None, bgr=False):
+    """Forward of a 3x3 stride-1 pad-1 conv with <= 4 output channels (the AdaAttN decoder's last conv,
+    AA/network.py:99) on vst_conv_thin_fwd: exact fp32 VALU, forward only (no autograd Function; the
+    training forward stays on Conv2dFn).  frames (N,H,W,3) uint8, Cout == 3: receives clamp(y, 0, 255)
+    truncated to uint8 (RGB, or BGR with bgr) in the same pass, and the call returns it without writing
+    the fp32 image unless `out` is given too; otherwise the fp32 image (N,Cout,H,W) is returned."""
+    x = _check(x, "conv input", 4).detach()
+    w = w.detach().contiguous()
+    N, Cin, H, W = x.shape
+    Cout = w.shape[0]
+    if tuple(w.shape) != (Cout, Cin, 3, 3) or (b is not None and tuple(b.shape) != (Cout,)):
+        raise VstError(f"conv_thin_fwd: x{tuple(x.shape)} w{tuple(w.shape)}")
+    if out is None and frames is None:
+        out = _empty((N, Cout, H, W), x)
+    if out is not None and tuple(out.shape) != (N, Cout, H, W):
+        raise VstError(f"conv_thin_fwd: out shape {tuple(out.shape)} != {(N, Cout, H, W)}")
+    if frames is not None and tuple(frames.shape) != (N, H, W, 3):
+        raise VstError(f"conv_thin_fwd: frames shape {tuple(frames.shape)} != {(N, H, W, 3)}")
+    bias = b.detach().contiguous() if b is not None else None
+    nbytes = 4.0 * (x.numel() + w.numel()) + (4.0 * N * Cout * H * W if out is not None else 0.0) \
+        + (3.0 * N * H * W if frames is not None else 0.0)
+    tok = kprof.begin(2.0 * N * Cout * H * W * Cin * 9, nbytes, ("thin_fwd", N, Cout, Cin, H, W), gemm_mode())
+    lib.vst_conv_thin_fwd(ptr(x), ptr(w), ptr(bias), ptr(out), None if frames is None else _ptr_u8(frames, "frames"),
+                          N, Cin, H, W, Cout, int(bool(reflect)), int(bool(bgr)), stream())
+    kprof.end(tok, family="thin")  # (a VALU kernel: outside the MFMA families' rooflines)
+    return out if frames is None else frames
+
+
 def conv_dgrad_padout(gz, w, x_shape, ks, pad, flops, dmask=None):
     """Stride-1 reflect-pad conv input gradient: the transposed GEMM over the padded grid writes
     its interior straight into dx and its border into a side buffer, folded into dx's border band."""

@@ -20,57 +20,20 @@ is not in this image) or, as an extension, a uint8 array (T,H,W,3) / iterable of
 frames.  Frames that are not 360x640 are resized by cv2 on the host exactly as the reference
 does (RC/utilities.py:120-122); without cv2 they raise.
 """
-import numpy as np
 import torch
 
 from .. import ops
+from ..video_io import FrameSource as _FrameSource
+from ..video_io import PinnedUploader, host_frame
 
 FRAME_HW = (360, 640)  # RC/utilities.py:121: cv2.resize(frame, (640, 360))
-
-
-def _cv2():
-    try:
-        import cv2  # noqa: PLC0415
-    except ImportError as e:  # pragma: no cover - cv2 is absent in this image
-        raise ImportError("reading video files / resizing frames needs OpenCV (cv2), as the reference does") from e
-    return cv2
-
-
-class _FrameSource:
-    """cv2.VideoCapture-like reader: `.read() -> (ret, frame)` over a path or in-memory frames."""
-
-    def __init__(self, video):
-        if isinstance(video, (str, bytes)) or hasattr(video, "__fspath__"):
-            self._cap = _cv2().VideoCapture(str(video))
-            self._it = None
-        else:
-            self._cap = None
-            self._it = iter(video)
-
-    def read(self):
-        if self._cap is not None:
-            return self._cap.read()
-        try:
-            return True, next(self._it)
-        except StopIteration:
-            return False, None
-
-    def release(self):
-        if self._cap is not None:
-            self._cap.release()
 
 
 def _host_frame(frame):
     """RC/utilities.py:119-122 host part: check / resize to 360x640 (cv2 INTER_LINEAR)."""
     if frame is None:
         raise ValueError("the video has fewer frames than input_frame_num / first_frame need")
-    frame = np.asarray(frame)
-    if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
-        raise ValueError(f"frames must be HxWx3 uint8 (cv2 BGR), got {frame.dtype} {frame.shape}")
-    if frame.shape[:2] != FRAME_HW:
-        cv2 = _cv2()
-        frame = cv2.resize(frame, (FRAME_HW[1], FRAME_HW[0]), interpolation=cv2.INTER_LINEAR)
-    return np.ascontiguousarray(frame)
+    return host_frame(frame, FRAME_HW, "INTER_LINEAR")
 
 
 def cvframe_to_tensor(frame, device="cuda"):
@@ -93,24 +56,12 @@ class _Stream:
 
     def __init__(self, reader, n, device, batch_frames):
         self.reader, self.n, self.device, self.B = reader, n, device, max(1, int(batch_frames))
-        self.pinned = None
+        self.uploader = PinnedUploader(device, max(self.B, n))
         self.history = None  # (n-1, 3, H, W) device frames preceding the next chunk
         self.eof = False
 
     def _upload(self, frames):
-        k = len(frames)
-        H, W = frames[0].shape[:2]
-        shape = (max(self.B, self.n), H, W, 3)
-        if self.pinned is None or tuple(self.pinned.shape) != shape:
-            self.pinned = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
-        host = self.pinned[:k].numpy()
-        for i, f in enumerate(frames):
-            host[i] = f
-        dev = self.pinned[:k].to(self.device, non_blocking=True)
-        out = ops.frames_to_tensor(dev)
-        # the pinned buffer is reused by the next chunk: wait for this copy first
-        torch.cuda.current_stream().synchronize()
-        return out
+        return self.uploader.upload(frames)
 
     def first(self, first_frame):
         """RC/utilities.py:196-206: skip to first_frame, read input_frame_num frames."""
