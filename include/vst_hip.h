@@ -185,6 +185,22 @@ int vst_tapsum(const float* P, float* dx, int N, int C, int H, int W, int K, int
 int vst_conv_dgrad_padout(const float* dy, const float* wpack, const float* mask, float* dx, float* border, int N,
                           int Cout, int Ho, int Wo, int Cin, int H, int W, int KS, int pad, void* workspace,
                           long ws_bytes, int mode, void* stream);
+/* The same data gradient for KS = 3, pad = 1 on the exact H x W grid, in one launch and without a
+ * border buffer: the zero-pad transposed conv (A = vst_pack_weight(transposed=1), K = 9 Cout) plus the
+ * terms the reflected border adds, computed inside the halo kernel from the dy patch each tile stages --
+ *   dx[ci][i][j] = sum_co sum_{kh,kw} w[co][ci][kh][kw] sum_{y in R_kh(i)} sum_{x in C_kw(j)} dy[co][y][x],
+ *   R_kh(i) = {i+1-kh} u ({0} if i == 1, kh == 0) u ({H-1} if i == H-2, kh == 2), C_kw(j) likewise over W
+ * (dy = 0 outside the image).  mask (optional, dx-shaped): dx = 0 where mask <= 0.  The summation
+ * order is fixed (an image in a batch equals the image alone); pixels outside rows {1, H-2} and columns
+ * {1, W-2} are bitwise those of vst_conv_dgrad_padout + vst_fold_border under VST_GEMM_NOSPLIT.
+ * vst_conv_dgrad_reflect3_workspace: -1 where the form does not apply (strict fp32 arithmetic,
+ * VST_GEMM_PERTAP, no VST_GEMM_KBLOCK, Cout % 16 != 0, a weight pack the halo block's M tile does not
+ * divide, H < 2 or W < 2) -- the caller keeps vst_conv_dgrad_padout, and vst_conv_dgrad_reflect3 returns
+ * VST_EUNSUPPORTED; otherwise the bytes of split-K workspace the launch uses (0: unsplit; a launch given
+ * less runs unsplit, as vst_conv_gemm does). */
+long vst_conv_dgrad_reflect3_workspace(int N, int Cout, int Cin, int H, int W, int mode);
+int vst_conv_dgrad_reflect3(const float* dy, const float* wpack, const float* mask, float* dx, int N, int Cout,
+                            int Cin, int H, int W, void* workspace, long ws_bytes, int mode, void* stream);
 /* Reflect-pad dgrad without the padded grid (ConvLayer / UpsampleConvLayer backward,
  * RC/network.py:72-75,114-120): core = vst_conv_gemm on the unpadded grid (up=1: GM_TRANSPOSED,
  * pad=KS/2; up=2: GM_ZERO stride 2, pad KS-1-KS/2, KS+1 taps with the weights of

@@ -1,7 +1,13 @@
 """Time the stride-1 reflect-pad data gradient of the residual convs (RC/network.py:145-150) on its
-two paths: the padded-grid GEMM (conv_dgrad_padout: per-tap kernel, interior + border side buffer)
-and core + ring (conv_dgrad_ring: the 3x3 core on the halo kernel, the padded grid's border ring as
-small GEMMs folded into dx's border band).  bf16x6 policy; interleaved rounds, median."""
+three paths: the padded-grid GEMM (conv_dgrad_padout: interior + border side buffer, then the fold --
+both launches are timed), core + ring (conv_dgrad_ring: the 3x3 core on the halo kernel, the padded
+grid's border ring as small GEMMs folded into dx's border band) and the exact grid
+(conv_dgrad_reflect3: one halo launch, the border's reflected taps in-kernel).  The residual shape
+16 x 192 x 64 x 128 under bf16x6 and an AdaAttN decoder shape under fp16; interleaved rounds, median.
+
+    python tools/dgrad_bench.py [--json out.json]
+"""
+import json
 import statistics
 import sys
 
@@ -10,35 +16,64 @@ import torch
 sys.path.insert(0, "video-style-transfer_amd")
 from vst import ops  # noqa: E402
 
+# (label, policy, scopes, N, Cout, Cin, H, W)
+CASES = [("residual 16x192x64x128", "bf16x6", ("stylizer", "res"), 16, 192, 192, 64, 128),
+         ("decoder 8x256x64x64", "f16", ("stylizer", "dec"), 8, 256, 256, 64, 64),
+         ("decoder 8x128x128x128 (Cout 128)", "f16", ("stylizer", "dec"), 8, 128, 128, 128, 128)]
 
-def main():
-    ops.use_policy("bf16x6")
+
+def run(label, policy, scopes, N, Cout, Cin, H, W, rounds=5, reps=5):
+    ops.use_policy(policy)
     dev = "cuda"
-    N, C, H, W = 16, 192, 64, 128
-    gz = torch.randn(N, C, H, W, device=dev)
-    w = torch.randn(C, C, 3, 3, device=dev) * 0.05
-    flops = 2.0 * N * C * H * W * C * 9
-    paths = {"padout": lambda: ops.conv_dgrad_padout(gz, w, (N, C, H, W), 3, 1, flops),
-             "ring": lambda: ops.conv_dgrad_ring(gz, w, (N, C, H, W), 3, 1, flops)}
-    with ops.gemm_scope("stylizer"), ops.gemm_scope("res"):
-        ops.gemm_role("dgrad")
-        out = {k: f() for k, f in paths.items()}
+    gz = torch.randn(N, Cout, H, W, device=dev)
+    w = torch.randn(Cout, Cin, 3, 3, device=dev) * 0.05
+    shape = (N, Cin, H, W)
+    flops = 2.0 * N * Cout * H * W * Cin * 9
+    res = {"case": label, "policy": policy}
+    with ops.gemm_scope(scopes[0]), ops.gemm_scope(scopes[1]):
+        mode = ops.gemm_role("dgrad")
+        nws = ops.dgrad_exact_workspace(N, Cout, Cin, H, W, mode)
+        paths = {"padout": lambda: ops.conv_dgrad_padout(gz, w, shape, 3, 1, flops),
+                 "ring": lambda: ops.conv_dgrad_ring(gz, w, shape, 3, 1, flops)}
+        if nws >= 0:
+            paths["exact"] = lambda: ops.conv_dgrad_reflect3(gz, w, shape, flops, nws)
+        out = {}
+        for k in list(paths):
+            try:
+                out[k] = paths[k]()
+            except ops.VstError as e:  # (a path that does not take this shape / mode)
+                print(f"  {k}: {e}")
+                del paths[k]
         torch.cuda.synchronize()
-        d = float((out["padout"] - out["ring"]).abs().max() / out["padout"].abs().max())
         times = {k: [] for k in paths}
-        for _ in range(5):
+        for _ in range(rounds):
             for k, f in paths.items():
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-                for _ in range(5):
+                for _ in range(reps):
                     f()
                 e1.record()
                 torch.cuda.synchronize()
-                times[k].append(e0.elapsed_time(e1) / 5)
+                times[k].append(e0.elapsed_time(e1) / reps)
+    print(f"{label} [{policy}]")
     for k, v in times.items():
         ms = statistics.median(v)
-        print(f"{k:8s} {ms*1e3:8.1f} us  {flops/ms/1e9:6.1f} TF/s")
-    print(f"max |padout - ring| / max |padout| = {d:.2e}")
+        res[k + "_us"] = round(ms * 1e3, 1)
+        res[k + "_us_min_max"] = [round(min(v) * 1e3, 1), round(max(v) * 1e3, 1)]
+        print(f"  {k:8s} {ms*1e3:8.1f} us  (min {min(v)*1e3:.1f}, max {max(v)*1e3:.1f})  {flops/ms/1e9:6.1f} TF/s")
+    for k in out:
+        if k != "padout":
+            d = float((out["padout"] - out[k]).abs().max() / out["padout"].abs().max())
+            res[f"padout_vs_{k}"] = d
+            print(f"  max |padout - {k}| / max |padout| = {d:.2e}")
+    return res
+
+
+def main():
+    results = [run(*c) for c in CASES]
+    if "--json" in sys.argv:
+        with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
+            json.dump(results, f, indent=1)
 
 
 if __name__ == "__main__":

@@ -401,7 +401,7 @@ static int conv_gemm_launch(const float* src, const float* wpack, const float* b
                             const float* gmask, int mode, void* stream, const float* ep_ra = nullptr,
                             const float* ep_rb = nullptr, const float* ep_rd = nullptr,
                             const float* ep_cg = nullptr, float* ph_border = nullptr, int ph_H = 0, int ph_W = 0,
-                            int ph_pad = 0, void* workspace = nullptr, long ws_bytes = 0) {
+                            int ph_pad = 0, void* workspace = nullptr, long ws_bytes = 0, bool reflect_t = false) {
   ConvParams P;
   P.ph_border = ph_border;
   P.ph_H = ph_H;
@@ -483,7 +483,12 @@ static int conv_gemm_launch(const float* src, const float* wpack, const float* b
     }
     dim3 grid(hp.tiles, P.Mpad / bm, N * S);
     const bool gm = gmask != nullptr;
-    if (am == VST_GEMM_BF16X6) launch_halo_prec<3>(gm, hcfg, KH, grid, st, P);
+    if (reflect_t) {  // the reflect-pad data gradient on the exact grid (conv_halo_kernel RT)
+      if (am == VST_GEMM_BF16X6) launch_halo_rt<3>(hcfg, grid, st, P);
+      else if (am == VST_GEMM_F16) launch_halo_rt<4>(hcfg, grid, st, P);
+      else if (am == VST_GEMM_BF16X3) launch_halo_rt<1>(hcfg, grid, st, P);
+      else launch_halo_rt<2>(hcfg, grid, st, P);
+    } else if (am == VST_GEMM_BF16X6) launch_halo_prec<3>(gm, hcfg, KH, grid, st, P);
     else if (am == VST_GEMM_F16) launch_halo_prec<4>(gm, hcfg, KH, grid, st, P);
     else if (am == VST_GEMM_BF16X3) launch_halo_prec<1>(gm, hcfg, KH, grid, st, P);
     else launch_halo_prec<2>(gm, hcfg, KH, grid, st, P);
@@ -495,6 +500,7 @@ static int conv_gemm_launch(const float* src, const float* wpack, const float* b
     }
     return vst_launch_status();
   }
+  if (reflect_t) return VST_EUNSUPPORTED;  // (the halo kernel only: vst_conv_dgrad_reflect3_workspace says when)
   int bm = cfg_bm(cfg), bn = cfg_bn(cfg);
   P.Mpad = (M + bm - 1) / bm * bm;
   P.K = K;
@@ -835,6 +841,29 @@ int vst_fold_border(const float* border, const float* mask, float* dx, long NC, 
   const long total = ((long)br * W + (long)(H - br) * bc) * NC;
   fold_border_kernel<<<ceil_div(total, 256), 256, 0, (hipStream_t)stream>>>(border, mask, dx, (int)NC, H, W, pad);
   return vst_launch_status();
+}
+
+// the halo plan of the reflect-pad 3x3 data gradient on the exact grid (hcfg 0: the form does not apply)
+static HaloPlan dgrad_reflect3_plan(int N, int Cout, int Cin, int H, int W, bool masked, int mode) {
+  if (H < 2 || W < 2) return HaloPlan{0, 1, 0, 0};
+  return halo_plan(N, Cout, Cin, H, W, 3, 3, GM_TRANSPOSED, 1, 1, 1, 1, masked ? EPI_MASK : 0, 0, mode);
+}
+
+long vst_conv_dgrad_reflect3_workspace(int N, int Cout, int Cin, int H, int W, int mode) {
+  if (!vst_mode_ok(mode) || N <= 0 || Cout <= 0 || Cin <= 0 || H <= 0 || W <= 0) return -1;
+  const HaloPlan hp = dgrad_reflect3_plan(N, Cout, Cin, H, W, false, mode);
+  return hp.hcfg ? splitk_bytes(hp, N, Cin, H, W) : -1;
+}
+
+int vst_conv_dgrad_reflect3(const float* dy, const float* wpack, const float* mask, float* dx, int N, int Cout,
+                            int Cin, int H, int W, void* workspace, long ws_bytes, int mode, void* stream) {
+  VST_CHECK_ARG(vst_mode_ok(mode));
+  VST_CHECK_ARG(ws_bytes >= 0 && (workspace || ws_bytes == 0));
+  VST_CHECK_ARG(dy && wpack && dx && N > 0 && Cout > 0 && Cin > 0 && H > 0 && W > 0);
+  if (!dgrad_reflect3_plan(N, Cout, Cin, H, W, mask != nullptr, mode).hcfg) return VST_EUNSUPPORTED;
+  return conv_gemm_launch(dy, wpack, nullptr, mask, dx, N, Cout, H, W, Cin, 9 * Cout, H, W, 3, 3, GM_TRANSPOSED, 1, 1,
+                          1, 1, mask ? EPI_MASK : 0, 0, nullptr, nullptr, mode, stream, nullptr, nullptr, nullptr,
+                          nullptr, nullptr, 0, 0, 0, workspace, ws_bytes, true);
 }
 
 int vst_fold_reflect(const float* dpad, float* dx, long NC, int Hs, int Ws, int pad, int up, int accumulate,

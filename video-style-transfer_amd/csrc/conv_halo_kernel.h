@@ -17,7 +17,9 @@
 // (tests/test_gpu_halo.py).  Covers every 3x3 stride-1 conv on the training paths: VGG16 / VGG19
 // convs (zero pad 1, RC/network.py:9-40, AA/vgg19.py:19-37), ReCoNet / AdaAttN residual and decoder
 // convs (reflect pad 1, RC/network.py:72-75,145-150, AA/network.py:9-33), and their data gradients
-// (the transposed gather over dY, zero pad; RC ResidualBlock's over the padded grid, EPI_PADOUT).
+// (the transposed gather over dY, zero pad; the reflect-pad 3x3 ones on the exact grid with the
+// border's reflected taps as extra MFMAs from the same patch -- the RT form below -- or, where that
+// form does not apply, over the padded grid, EPI_PADOUT).
 #pragma once
 #include "conv_gemm_kernel.h"
 
@@ -75,6 +77,39 @@ __device__ __forceinline__ void halo_tap(f32x16 (&acc)[1][TN], const bf16x8_t (&
   }
 }
 
+// The products of one A fragment with ONE B fragment whose lanes read their own patch pixel (p: the
+// lane's four dwords of piece 0; a lane that is not `live` contributes zeros) -- the border terms of the
+// reflect-pad data gradient (conv_halo_kernel RT).  Product order per fragment as in halo_tap.
+template <int PREC>
+__device__ __forceinline__ void halo_frag(f32x16& acc, const bf16x8_t (&ar)[1][3], const float* p, bool live) {
+  constexpr int NPC = PREC == 3 ? 3 : PREC == 1 ? 2 : 1;
+  bf16x8_t c[3];
+#pragma unroll
+  for (int pc = 0; pc < NPC; ++pc) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(p + 8 * pc);
+    c[pc] = __builtin_bit_cast(bf16x8_t, live ? v : u32x4{0u, 0u, 0u, 0u});
+  }
+  f32x16 a = acc;
+  if constexpr (PREC == 3) {
+    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][2], c[0], a, 0, 0, 0);
+    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][1], c[1], a, 0, 0, 0);
+    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][0], c[2], a, 0, 0, 0);
+    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][1], c[0], a, 0, 0, 0);
+    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][0], c[1], a, 0, 0, 0);
+    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][0], c[0], a, 0, 0, 0);
+  } else if constexpr (PREC == 1) {
+    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][1], c[0], a, 0, 0, 0);
+    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][0], c[1], a, 0, 0, 0);
+    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][0], c[0], a, 0, 0, 0);
+  } else if constexpr (PREC == 4) {
+    a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, ar[0][0]), __builtin_bit_cast(f16x8_t, c[0]),
+                                               a, 0, 0, 0);
+  } else {
+    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][0], c[0], a, 0, 0, 0);
+  }
+  acc = a;
+}
+
 // Block = WM x WN waves: wave (wm, wn) computes weight rows m0 + 32 wm .. +31 for output rows
 // oy0 + 4 wn .. +3 (TN = 4 fragments of 32 pixels), so the tile is TH = 4 WN rows x 32 columns and
 // the patch (TH + 2) x 34 pixels.  DB: double-buffered patch (the next channel block's stores need
@@ -91,8 +126,25 @@ __device__ __forceinline__ void halo_tap(f32x16 (&acc)[1][TN], const bf16x8_t (&
 // RC/network.py:78-85,158 -- patch (TH + 8) x 32, nine row taps, column pad P.pad_x = 0); 1 x 9
 // (ConvTanh's row-split forward, RC/network.py:78-85: GEMM rows (co, kh), nine column taps over the
 // reflect-padded rows -- patch TH x 40, on the 32-row block H1x4S).
-template <int WM, int WN, int MINW, int PREC, bool GM, bool DB, int PD = 1, int KH = 3, int KW = KH>
+// RT: the data gradient of a reflect-pad-1 3x3 stride-1 conv on the exact H x W grid (gmode
+// GM_TRANSPOSED, pad 1: the zero-pad transposed conv's grid, patch and K walk) plus the terms the
+// reflected border adds, each read from the patch the tile stages anyway:
+//   dx[i][j] = sum_{kh,kw} w[kh][kw] . sum_{y in R_kh(i)} sum_{x in C_kw(j)} dy[y][x]
+//   R_kh(i) = {i+1-kh} u ({0} if i == 1 and kh == 0) u ({H-1} if i == H-2 and kh == 2), C_kw(j) likewise.
+// Row terms: the wave holding output row 1 (H-2) issues, behind tap (0, kw) ((2, kw)), one more
+// fragment's products into that row's accumulator with B from dy row 0 (H-1).  Column terms: the waves of
+// the tiles holding column 1 (W-2) issue, behind tap (kh, 0) ((kh, 2)), each fragment's products once more
+// with B = dy[.][0] (dy[.][W-1]) in the lane of that column and zeros in every other lane; the corner
+// pixels' (row term of the column term) the same way on the row term's fragment.  Every extra follows the
+// tap whose weights it uses, so the summation order is fixed; pixels outside rows {1, H-2} and columns
+// {1, W-2} are bitwise those of the padded-grid form.
+// (Collecting the column terms of a wave's four rows in ONE extra accumulator fragment and moving them
+// across lanes after the K loop would cost 3 fragment-taps on 36 instead of 12, but its 16 accumulator
+// registers do not fit: the bf16x6 2x2 one-buffer tile, 162 VGPRs of the 168 that 3 waves per SIMD allow,
+// spilled 36 with it, the fp16 one 442 -- DESIGN.md section 4.10.)
+template <int WM, int WN, int MINW, int PREC, bool GM, bool DB, int PD = 1, int KH = 3, int KW = KH, bool RT = false>
 __global__ __launch_bounds__(WM * WN * 64, MINW) void conv_halo_kernel(ConvParams P) {
+  static_assert(!RT || (KH == 3 && KW == 3 && !GM), "reflect-transposed form: 3x3 taps, no gather mask");
   static_assert(PREC >= 1 && PREC <= 4, "halo kernel: bf16x3, bf16x6, bf16 or fp16 products");
   static_assert((KH == KW && (KH == 2 || KH == 3)) || (KH == 9 && KW == 1) || (KH == 1 && KW == 9),
                 "halo kernel: 2x2, 3x3, 9x1 or 1x9 taps");
@@ -169,6 +221,13 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void conv_halo_kernel(ConvParam
   for (int j = 0; j < TN; ++j)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[0][j][r] = 0.f;
+
+  // RT: which border terms this tile / wave owns (block- / wave-uniform)
+  const int rt_cw_lo = P.Wo - 2 - ox0;  // tile column of output column W-2
+  const bool rt_c1 = RT && ox0 == 0, rt_cw = RT && rt_cw_lo >= 0 && rt_cw_lo < HTW;
+  const int wn_u = __builtin_amdgcn_readfirstlane(wn);
+  const int rt_jb = P.Ho - 2 - oy0 - 4 * wn_u;  // fragment of output row H-2
+  const bool rt_top = RT && oy0 == 0 && wn_u == 0, rt_bot = RT && rt_jb >= 0 && rt_jb < 4;
 
   const int nst_all = P.Cs / 16;
   const int st0 = __builtin_amdgcn_readfirstlane(ks * nst_all / P.ksplit);
@@ -248,6 +307,37 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void conv_halo_kernel(ConvParam
             __builtin_bit_cast(bf16x8_t, __builtin_amdgcn_raw_buffer_load_b128(asrd, ad_voff, a_soff + 32 * pc, 0));
     }
   };
+  // RT: the border terms under tap (kh, kw), behind its products and with its A fragments.  Every
+  // source is one of three lane offsets into the patch (floats; the wave's first patch row at the lane's
+  // column, at dy column 0 and at dy column W-1) plus a compile-time constant: dy row 0 is patch row
+  // 4 wn + 1 of the wave that owns output row 1 (wn = 0), dy row H-1 patch row 4 wn + j + 2 for the
+  // fragment j of output row H-2 -- so the reads carry immediate offsets and hold no address registers
+  const int rt_o = (4 * wn * HPW + lo) * LS + 4 * hi, rt_o1 = (4 * wn * HPW + 1) * LS + 4 * hi;
+  const int rt_ow = (4 * wn * HPW + P.Wo - ox0) * LS + 4 * hi;
+  auto rt_extras = [&](int kh, int kw, int buf, const bf16x8_t (&ar)[1][3]) {
+    const float* pb = &Ps[buf][0][0];
+    const int ph = KH - 1 - kh, pw = KW - 1 - kw;
+    // the column term's source (dy column 0 / W-1) and the lane of its output column
+    const bool cx = (kw == 0 && rt_c1) || (kw == 2 && rt_cw);
+    const float* px = pb + (kw == 0 ? rt_o1 : rt_ow);
+    const bool cx_lane = lo == (kw == 0 ? 1 : rt_cw_lo);
+    if (kh == 0 && rt_top) {  // output row 1 += w[0][kw] . dy row 0
+      halo_frag<PREC>(acc[0][1], ar, pb + rt_o + (HPW + pw) * LS, true);
+      if (cx) halo_frag<PREC>(acc[0][1], ar, px + HPW * LS, cx_lane);
+    }
+    if (kh == 2 && rt_bot) {  // output row H-2 += w[2][kw] . dy row H-1
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+        if (j == rt_jb) {
+          halo_frag<PREC>(acc[0][j], ar, pb + rt_o + ((j + 2) * HPW + pw) * LS, true);
+          if (cx) halo_frag<PREC>(acc[0][j], ar, px + (j + 2) * HPW * LS, cx_lane);
+        }
+    }
+    if (cx) {  // output column 1 (W-2) += w[kh][0] . dy column 0 (w[kh][2] . dy column W-1)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) halo_frag<PREC>(acc[0][j], ar, px + (j + ph) * HPW * LS, cx_lane);
+    }
+  };
   // the taps of every channel block of stage st, B fragments from patch buffer buf
   auto taps = [&](int cb, int buf) {
 #pragma unroll
@@ -263,6 +353,7 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void conv_halo_kernel(ConvParam
         const int kt_next = t < NTAP - 1 ? NTAP * cb + t + 1 : (cb + 1 < nst ? NTAP * (cb + 1) : 0);
         load_a(kt_next, arN);
         halo_tap<TN, PREC, LS>(acc, arC, Bt, lane, HPW);
+        if constexpr (RT) rt_extras(kh, kw, buf, arC);
 #pragma unroll
         for (int pc = 0; pc < NPC; ++pc) arC[0][pc] = arN[0][pc];
       } else {
@@ -270,8 +361,10 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void conv_halo_kernel(ConvParam
         if (t < APRE) {
           const bf16x8_t a1[1][3] = {{arS[t][0], arS[t][1], arS[t][2]}};
           halo_tap<TN, PREC, LS>(acc, a1, Bt, lane, HPW);
+          if constexpr (RT) rt_extras(kh, kw, buf, a1);
         } else {
           halo_tap<TN, PREC, LS>(acc, arC, Bt, lane, HPW);
+          if constexpr (RT) rt_extras(kh, kw, buf, arC);
         }
         if (t + 1 >= APRE && t + 1 < NTAP) {
 #pragma unroll
@@ -370,9 +463,10 @@ constexpr int halo_wn_c(int c) { return c == H2x4S || c == H1x4S ? 4 : (c == H2x
 constexpr bool halo_db_c(int c) { return !(c == H2x2S || c == H2x4S || c == H3x1S || c == H3x2S || c == H4x2S || c == H1x4S); }
 inline int halo_wm(int c) { return halo_wm_c(c); }
 inline int halo_wn(int c) { return halo_wn_c(c); }
-// 0: the per-tap kernel (the M tile would not divide the pack's Mpad).  (The bf16x6 residual data
-// gradient over the padded grid -- 66 x 130, a fifth of a 32-column tile grid wasted -- is slower than
-// per-tap on the 2x4 block and faster on the 2x2 one, measured above: it runs here.)
+// 0: the per-tap kernel (the M tile would not divide the pack's Mpad).  (The residual data gradient
+// runs the RT form on the exact 64 x 128 grid, 32 tiles of 8 x 32; over the padded 66 x 130 grid it
+// needed 9 x 5 = 45, 1.41x the MFMA work -- that form, slower than per-tap on the 2x4 block and faster
+// on the 2x2 one as measured above, remains for the layers the RT form does not take.)
 inline int halo_cfg(int M, int pack_mpad) {
   int c;
   if (M <= 64) c = HALO_M64;
@@ -392,7 +486,7 @@ constexpr int HALO_SMINW_SP = 3;
 // of the taps and the taps' A loads ahead of them, a second patch in flight would still be waited for by
 // the first per-tap A load after it (vector loads complete in order)
 constexpr int HALO_PD = 1;
-template <int C, int PR, bool GM, int KH = 3, int KW = KH>
+template <int C, int PR, bool GM, int KH = 3, int KW = KH, bool RT = false>
 void launch_halo_c(dim3 grid, hipStream_t st, const ConvParams& P) {
   constexpr int WM = halo_wm_c(C), WN = halo_wn_c(C);
   // waves per SIMD the registers must allow: one-buffer tiles 4 for the single-product modes (their
@@ -400,11 +494,13 @@ void launch_halo_c(dim3 grid, hipStream_t st, const ConvParams& P) {
   // budget (measured: the spilling 2x2 tile 1088 us vs 758 us at 3 waves per SIMD on the 64-row VGG
   // layer; fp16 at 4 waves 118 us vs 150 us at 3 on the residual layer); 3 for 4-wave double-
   // buffered tiles, 2 for the 6- and 8-wave double-buffered ones
-  constexpr int MINW = !halo_db_c(C) ? (PR == 3 || PR == 1 ? 3 : HALO_SMINW_SP) : (WM * WN <= 4 ? 3 : 2);
+  // (the RT form: 2 -- its conditional border terms do not fit the 168 VGPRs of 3 waves per SIMD on any
+  // 4-wave tile: 47-237 spilled registers)
+  constexpr int MINW = RT ? 2 : !halo_db_c(C) ? (PR == 3 || PR == 1 ? 3 : HALO_SMINW_SP) : (WM * WN <= 4 ? 3 : 2);
   // depth-2 patch prefetch (round 4: config 5 145.07 -> 141.5 ms, profiles/r04_halo_pd.txt) is off
   // (HALO_PD above)
   constexpr int PD = (PR != 3 && halo_db_c(C) && WM * WN >= 8) ? HALO_PD : 1;
-  conv_halo_kernel<WM, WN, MINW, PR, GM, halo_db_c(C), PD, KH, KW><<<grid, WM * WN * 64, 0, st>>>(P);
+  conv_halo_kernel<WM, WN, MINW, PR, GM, halo_db_c(C), PD, KH, KW, RT><<<grid, WM * WN * 64, 0, st>>>(P);
 }
 
 // only the block shapes the build's selection can reach are instantiated
@@ -440,6 +536,15 @@ void launch_halo19(dim3 grid, hipStream_t st, const ConvParams& P) {
   launch_halo_c<H1x4S, PR, false, 1, 9>(grid, st, P);
 }
 
+// the reflect-transposed 3x3 form (conv_halo_kernel RT; no gather mask)
+template <int PR>
+void launch_halo_rt(int c, dim3 grid, hipStream_t st, const ConvParams& P) {
+  if (c == HALO_M64) launch_halo_c<HALO_M64, PR, false, 3, 3, true>(grid, st, P);
+  else if (c == HALO_M128) launch_halo_c<HALO_M128, PR, false, 3, 3, true>(grid, st, P);
+  else if (c == HALO_M192) launch_halo_c<HALO_M192, PR, false, 3, 3, true>(grid, st, P);
+  else launch_halo_c<HALO_M256, PR, false, 3, 3, true>(grid, st, P);
+}
+
 template <int PR>
 void launch_halo_prec(bool gm, int c, int kh, dim3 grid, hipStream_t st, const ConvParams& P) {
   if (kh == 2) launch_halo2<PR>(c, grid, st, P);
@@ -452,5 +557,9 @@ extern template void launch_halo_prec<1>(bool, int, int, dim3, hipStream_t, cons
 extern template void launch_halo_prec<2>(bool, int, int, dim3, hipStream_t, const ConvParams&);
 extern template void launch_halo_prec<3>(bool, int, int, dim3, hipStream_t, const ConvParams&);
 extern template void launch_halo_prec<4>(bool, int, int, dim3, hipStream_t, const ConvParams&);
+extern template void launch_halo_rt<1>(int, dim3, hipStream_t, const ConvParams&);
+extern template void launch_halo_rt<2>(int, dim3, hipStream_t, const ConvParams&);
+extern template void launch_halo_rt<3>(int, dim3, hipStream_t, const ConvParams&);
+extern template void launch_halo_rt<4>(int, dim3, hipStream_t, const ConvParams&);
 
 }  // namespace vstk

@@ -3,4 +3,5 @@
 
 namespace vstk {
 template void launch_halo_prec<4>(bool, int, int, dim3, hipStream_t, const ConvParams&);
+template void launch_halo_rt<4>(int, dim3, hipStream_t, const ConvParams&);
 }  // namespace vstk

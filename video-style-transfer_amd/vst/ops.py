@@ -394,7 +394,7 @@ def splitk_workspace(like, *geom):
 def conv_dgrad(gz, w, x_shape, ks, stride, pad, pad_mode, up, gmask=None, dmask=None):
     """Input gradient of (upsample x`up` -> pad -> conv(stride)) given the conv-output grad gz;
     dmask: multiply the result by (dmask > 0) in the GEMM epilogue (zero-pad path, and the
-    stride-1 reflect-pad padded-grid path with its border fold)."""
+    stride-1 reflect-pad paths: the 3x3 exact-grid launch, the padded grid with its border fold)."""
     gemm_role("dgrad")
     N, Cin, H, W = x_shape
     Cout = w.shape[0]
@@ -425,6 +425,10 @@ def conv_dgrad(gz, w, x_shape, ks, stride, pad, pad_mode, up, gmask=None, dmask=
         dm = dmask.contiguous() if dmask is not None else None
         if kwu_ok(Cout, ks, stride, up, _round4(W + 2 * pad)) and w.shape[2] == ks:
             return conv_dgrad_padout_kwu(gz, w, x_shape, ks, pad, flops, dm)
+        if ks == 3 and pad == 1 and tuple(w.shape[2:]) == (3, 3) and (gemm_mode() & 7) in DGRAD_EXACT_MODES:
+            nws = dgrad_exact_workspace(N, Cout, Cin, H, W, gemm_mode())
+            if nws >= 0:
+                return conv_dgrad_reflect3(gz, w, x_shape, flops, nws, dm)
         return conv_dgrad_padout(gz, w, x_shape, ks, pad, flops, dm)
     if stride == 1 and gmask is None and ks % 2 == 1 and ks > 1 and pad == ks // 2 and min(H, W) * up > ks + 1:
         return conv_dgrad_ring(gz, w, x_shape, ks, up, flops)
@@ -505,6 +509,44 @@ def conv_dgrad_padout(gz, w, x_shape, ks, pad, flops, dmask=None):
                               ptr(ws), nws, mode, stream())
     kprof.end(tok)
     lib.vst_fold_border(ptr(border), ptr(dmask), ptr(dx), N * Cin, H, W, pad, stream())
+    return dx
+
+
+DGRAD_EXACT = os.environ.get("VST_DGRAD_EXACT", "1") != "0"  # A/B: reflect-pad 3x3 data gradients on the exact grid
+# ... under the split-product modes.  The single-product ones (fp16, bf16) keep the padded grid: config 5
+# (fp16, 512x1024) measured 119.8 ms on the parent against 121.0 ms with them on the exact grid, one run
+# each -- not shown to be no slower there, although the kernel alone is faster at the decoder shapes
+# (tools/dgrad_bench.py)
+DGRAD_EXACT_MODES = (GEMM_MODES["bf16x6"], GEMM_MODES["bf16x3"])
+_DGRAD_EXACT_WS = {}  # (N, Cout, Cin, H, W, mode) -> vst_conv_dgrad_reflect3_workspace (host arithmetic)
+
+
+def dgrad_exact_workspace(N, Cout, Cin, H, W, mode):
+    """Split-K workspace bytes of vst_conv_dgrad_reflect3 for this geometry, or -1 where the exact-grid
+    form does not apply (or VST_DGRAD_EXACT=0): the caller keeps the padded-grid path."""
+    if not DGRAD_EXACT:
+        return -1
+    key = (N, Cout, Cin, H, W, mode)
+    nb = _DGRAD_EXACT_WS.get(key)
+    if nb is None:
+        nb = _DGRAD_EXACT_WS[key] = int(lib.vst_conv_dgrad_reflect3_workspace(*key))
+    return nb
+
+
+def conv_dgrad_reflect3(gz, w, x_shape, flops, nws, dmask=None):
+    """Stride-1 reflect-pad-1 3x3 conv input gradient on the exact grid: one halo-kernel launch, the
+    reflected border's taps computed in-kernel (no border buffer, no fold)."""
+    N, Cin, H, W = x_shape
+    Cout = w.shape[0]
+    wp = packed_weight(w, transposed=True)
+    dx = _empty(x_shape, gz)
+    mode = gemm_mode()
+    ws = _empty(((nws + 3) // 4,), gz) if nws > 0 and SPLITK else None
+    tok = kprof.begin(flops, 4.0 * (gz.numel() + wp.numel() + dx.numel()),
+                      (N, Cout, H, W, Cin, H, W, 3, 3, GM_TRANSPOSED, 1, 1, 1), mode)
+    lib.vst_conv_dgrad_reflect3(ptr(gz), ptr(wp), ptr(dmask), ptr(dx), N, Cout, Cin, H, W, ptr(ws),
+                                nws if ws is not None else 0, mode, stream())
+    kprof.end(tok)
     return dx
 
 
