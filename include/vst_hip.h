@@ -521,6 +521,35 @@ int vst_pfm_read_header(const char* path, int* width, int* height, int* channels
                         float* scale);
 int vst_pfm_read(const char* path, void* dst, long bytes, int offset);
 
+/* ---- evaluation metrics (csrc/metrics.hip) --------------------------------------------------
+ * Fused masked warping error of B frame pairs (RT/utilities.py:231-236 temporal_errors_sintel: mask *
+ * MSELoss(none)(styled0, warp(styled1, flow)), .mean(); AA/exps_sintel.py:79-100: clamp(0,255)/255 of
+ * both frames, mask * L1Loss(none)(cs2, warp(cs1, flow)), sum / (C H W)):
+ *   acc[0] += scale * sum over (B, C, H, W) of mask * |a - warp(b, flo)|^power,  acc[1] += B
+ * (acc: two doubles on the device; a scene accumulates without a host sync).  The warp is vst_warp_fwd's
+ * (bilinear, zeros padding, taps nw, ne, sw, se) and is never written out.  power: 1 or 2.  mask:
+ * B x H x W, broadcast over channels, NULL = ones.  flo_hwc = 1: flo is B x H x W x 2 (a .flo payload
+ * as it lies in the file, RT/utilities.py:113-152) instead of B x 2 x H x W.  clamp_unit = 1: every
+ * value of a and every gathered tap of b goes through clamp(0, 255) / 255 first.  The sum runs in
+ * fp64 in a fixed order (bitwise reproducible).  workspace: vst_temporal_error_workspace bytes,
+ * 8-byte aligned. */
+long vst_temporal_error_workspace(int B, int H, int W);
+int vst_temporal_error(const float* a, const float* b, const float* flo, const float* mask, int B, int C, int H, int W,
+                       int power, int flo_hwc, int clamp_unit, double scale, void* workspace, double* acc,
+                       void* stream);
+/* SSIMMetric.forward (AA/eval.py:191-223): depthwise win x win Gaussian window (win odd, <= 11) over
+ * planes zero-padded by win / 2, the five moments mu1, mu2, E[x^2], E[y^2], E[xy], the SSIM map with
+ * C1 = 0.01^2, C2 = 0.03^2, out[b] = mean over channels of the plane means; map (may be NULL) receives
+ * the B x C x H x W map.  taps: the win 1-D window values in HOST memory (read during the call; the
+ * reference's 2-D window is their outer product, AA/eval.py:180-184).  tile: 0 the default tile,
+ * 1 = 32 x 32, 2 = 64 x 16 (tools/eval_bench.py).  workspace: vst_ssim_workspace bytes, 8-byte aligned. */
+long vst_ssim_workspace(int B, int C, int H, int W);
+int vst_ssim(const float* img1, const float* img2, const float* taps, int win, int B, int C, int H, int W, float* out,
+             float* map, void* workspace, int tile, void* stream);
+/* compute_histogram (AA/eval.py:38-46, np.bincount(img[:, :, ch].flatten(), minlength=256), without
+ * its + 1): images = N x H x W x C uint8 (C = 1 or 3), hist = N x C x 256 int32, overwritten. */
+int vst_hist_u8(const void* images, void* hist, int N, int H, int W, int C, void* stream);
+
 /* ---- gradient sums / fills -----------------------------------------------------------------
  * out[i] = ((a[i] + b[i]) + c[i]) + d[i] over n floats, NULL addends skipped (a..d: at least one);
  * out may be one of the addends.  The autograd gradient sum of a tensor with several consumers

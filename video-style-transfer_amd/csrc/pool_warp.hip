@@ -189,29 +189,7 @@ inline dim3 pool_vec_grid(long NC, int rows, int W) {
   return dim3((unsigned)ceil_div((long)(W >> 2), 64), (unsigned)ceil_div((long)rows, 4), (unsigned)NC);
 }
 
-struct Bilin {
-  int x0, y0;
-  float w[4];  // nw, ne, sw, se
-};
-
-// grid_sample(align_corners=False) bilinear coordinates + weights, same fp32 op order as ATen
-__device__ __forceinline__ Bilin warp_coords(int x, int y, float u, float v, int H, int W) {
-  float gx = 2.0f * ((float)x + u) / (float)max(W - 1, 1) - 1.0f;
-  float gy = 2.0f * ((float)y + v) / (float)max(H - 1, 1) - 1.0f;
-  float ix = ((gx + 1.f) * W - 1.f) / 2.f;
-  float iy = ((gy + 1.f) * H - 1.f) / 2.f;
-  float fx = floorf(ix), fy = floorf(iy);
-  Bilin b;
-  b.x0 = (int)fx;
-  b.y0 = (int)fy;
-  float ix_se = fx + 1.f, iy_se = fy + 1.f;
-  b.w[0] = (ix_se - ix) * (iy_se - iy);
-  b.w[1] = (ix - fx) * (iy_se - iy);
-  b.w[2] = (ix_se - ix) * (iy - fy);
-  b.w[3] = (ix - fx) * (iy - fy);
-  return b;
-}
-
+// (Bilin / warp_coords: vst_common.h, shared with the fused temporal error of metrics.hip)
 __global__ void warp_fwd_kernel(const float* __restrict__ x, const float* __restrict__ flo, float* __restrict__ out,
                                 int B, int C, int H, int W) {
   long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -63,6 +63,33 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Flow-warp sampling (RC/utilities.py:39-57, RT/utilities.py:59-77: grid normalised by (W-1)/(H-1),
+// then grid_sample with align_corners=False), shared by the warp kernels of pool_warp.hip and the fused
+// temporal error of metrics.hip so that both sample one arithmetic.
+struct Bilin {
+  int x0, y0;
+  float w[4];  // nw, ne, sw, se
+};
+
+// grid_sample(align_corners=False) bilinear coordinates + weights, same fp32 op order as ATen
+__device__ __forceinline__ Bilin warp_coords(int x, int y, float u, float v, int H, int W) {
+  float gx = 2.0f * ((float)x + u) / (float)max(W - 1, 1) - 1.0f;
+  float gy = 2.0f * ((float)y + v) / (float)max(H - 1, 1) - 1.0f;
+  float ix = ((gx + 1.f) * W - 1.f) / 2.f;
+  float iy = ((gy + 1.f) * H - 1.f) / 2.f;
+  float fx = floorf(ix), fy = floorf(iy);
+  Bilin b;
+  b.x0 = (int)fx;
+  b.y0 = (int)fy;
+  float ix_se = fx + 1.f, iy_se = fy + 1.f;
+  b.w[0] = (ix_se - ix) * (iy_se - iy);
+  b.w[1] = (ix - fx) * (iy_se - iy);
+  b.w[2] = (ix_se - ix) * (iy - fy);
+  b.w[3] = (ix - fx) * (iy - fy);
+  return b;
+}
+
+
 // GEMM arithmetic mode: a per-call argument of every GEMM / pack entry (vst_hip.h VST_GEMM_*, plus
 // the VST_GEMM_KBLOCK K-order flag); the library keeps no mode state
 static inline int vst_mode_arith(int mode) { return mode & 7; }

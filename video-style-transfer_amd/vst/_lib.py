@@ -37,6 +37,8 @@ _CTYPES = {
     "int": ctypes.c_int,
     "long": ctypes.c_long,
     "float": ctypes.c_float,
+    "double": ctypes.c_double,
+    "double*": ctypes.c_void_p,
     "void": None,
     "void*": ctypes.c_void_p,
     "float*": ctypes.c_void_p,
