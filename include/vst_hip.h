@@ -550,6 +550,34 @@ int vst_ssim(const float* img1, const float* img2, const float* taps, int win, i
  * its + 1): images = N x H x W x C uint8 (C = 1 or 3), hist = N x C x 256 int32, overwritten. */
 int vst_hist_u8(const void* images, void* hist, int N, int H, int W, int C, void* stream);
 
+/* ---- LPIPS (csrc/lpips.hip) -----------------------------------------------------------------
+ * The distance head of one trunk level (AA/lpips/__init__.py:13-15 normalize_tensor on both features,
+ * AA/lpips/lpips.py:139-152: the squared difference, the 1x1 NetLinLayer conv or -- lpips=False -- the
+ * channel sum, spatial_average) in one pass.  f0, f1: N images of [C][P] fp32 planes (P = h w), image n
+ * at f + n * bs floats (bs >= C P: the two halves of one 2N trunk batch need no copy).  Per pixel
+ *   na = sqrt(sum_c a_c^2), nb likewise, d = sum_c w_c (a_c / (na + 1e-10) - b_c / (nb + 1e-10))^2
+ * in this difference form (the quotients are products with a reciprocal of (n + 1e-10) taken once per
+ * pixel), so f1 == f0 gives exactly 0.  w: [C] on the device, NULL = ones.  layer[n] = mean_p d;
+ * total[n] = layer[n] (accumulate = 0) or total[n] + layer[n] (accumulate = 1: five calls on one stream
+ * sum the levels in the reference's order); map (may be NULL): [N][P] = d (spatial=True,
+ * AA/lpips/lpips.py:144-150).  Each feature element is read from HBM once and kept in registers; the
+ * channels of a pixel are split over the block and combined by wave shuffles and LDS in a fixed order;
+ * the pixel sum runs in fp64 over per-block partials in `workspace` and a finishing kernel (no float atomics: bitwise
+ * reproducible, and image n of a batch is bitwise the image alone).  P <= 4096 runs 32-pixel blocks
+ * (the deep levels), larger P 64-pixel blocks.  C: a multiple of 16, at most 512.  workspace:
+ * vst_lpips_head_workspace bytes, 8-byte aligned. */
+long vst_lpips_head_workspace(int N, int C, long P);
+int vst_lpips_head(const float* f0, long f0_bs, const float* f1, long f1_bs, const float* w, int N, int C, long P,
+                   float* layer, float* total, int accumulate, float* map, void* workspace, void* stream);
+/* im2tensor + ScalingLayer (AA/lpips/__init__.py:86-88, AA/lpips/lpips.py:130-135,164-171) in one pass
+ * into images [batch_offset, batch_offset + N) of out ([..][3][H][W] fp32).  src_u8 = 1: src is N x H x W
+ * x 3 uint8 (swap_rb: BGR frames), t = float(double(v) / 127.5 - 1.0) -- numpy's float64, then
+ * torch.Tensor; src_u8 = 0: src is N x 3 x H x W fp32, t = normalize ? 2 x - 1 : x.  scaling = 1 (version
+ * "0.1"): out = (t - shift_c) / scale_c in fp32, shift = (-0.030, -0.088, -0.188), scale = (0.458, 0.448,
+ * 0.450); scaling = 0 (version "0.0"): out = t. */
+int vst_lpips_input(const void* src, int src_u8, float* out, long batch_offset, int N, int H, int W, int swap_rb,
+                    int normalize, int scaling, void* stream);
+
 /* ---- gradient sums / fills -----------------------------------------------------------------
  * out[i] = ((a[i] + b[i]) + c[i]) + d[i] over n floats, NULL addends skipped (a..d: at least one);
  * out may be one of the addends.  The autograd gradient sum of a tensor with several consumers

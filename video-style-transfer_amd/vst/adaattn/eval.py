@@ -1,14 +1,15 @@
-"""Drop-in for the SSIM / Gram / KL entries of AA/eval.py on HIP kernels (vst.metrics).
+"""Drop-in for the LPIPS / SSIM / Gram / KL entries of AA/eval.py on HIP kernels (vst.metrics, vst.lpips).
 
 `opt` is the reference's argparse namespace (`path0`, `path1`, `device`); `no_print=True` returns the
 value instead of printing it, as in the reference.  Image files are read with cv2 when it is
-importable and with Pillow otherwise.  Not carried: lpips_loss and sifid (downloaded trunk weights)
-and nth_order_moment / uniformity / average_entropy (OpenCV's BGR2GRAY), DESIGN.md 4.11.
+importable and with Pillow otherwise.  Not carried: sifid (an InceptionV3 trunk whose weights are a
+download) and nth_order_moment / uniformity / average_entropy (OpenCV's BGR2GRAY), DESIGN.md 4.11.
 """
 import torch
 
 from .. import ops
-from ..metrics import SSIMMetric, gram_distance, imread, kl_divergence  # noqa: F401
+from ..lpips import LPIPS
+from ..metrics import SSIMMetric, gram_distance, imread, kl_divergence, lpips_distance  # noqa: F401
 from .vgg19 import VGG19
 
 
@@ -16,6 +17,21 @@ def _frame(path, device, bgr):
     """The file as a (1,3,H,W) fp32 tensor in [0,255]: planes in RGB order (bgr=True swaps cv2's
     BGR, `cv2_to_tensor(cv2.imread(p))`), or in the file's BGR order."""
     return ops.frames_to_tensor(torch.from_numpy(imread(path)).to(device).unsqueeze(0), bgr=bgr)
+
+
+def lpips_loss(opt, no_print=False):
+    """AA/eval.py:19-35.  The model is built once and kept on the function like the reference's; assign
+    `lpips_loss.loss_fn` beforehand to evaluate with given weights.  The files go to the device as uint8
+    frames; im2tensor and the ScalingLayer are one kernel pass there."""
+    if not hasattr(lpips_loss, "loss_fn"):
+        lpips_loss.loss_fn = LPIPS(net="vgg").to(opt.device)
+    img0 = torch.from_numpy(imread(opt.path0)).to(opt.device).unsqueeze(0)
+    img1 = torch.from_numpy(imread(opt.path1)).to(opt.device).unsqueeze(0)
+    dist01 = lpips_distance(lpips_loss.loss_fn, img0, img1, bgr=True)
+    if not no_print:
+        print("Distance: %f" % dist01.item())
+    else:
+        return dist01.item()
 
 
 def kl_loss(opt, no_print=False):

@@ -1,0 +1,276 @@
+"""Drop-in MI355X implementation of the reference's `lpips` package (AA/lpips/) for its VGG trunk:
+`LPIPS(net="vgg")`, the default mode of AA/eval.py and the first two columns of AA/exps_image.py.
+
+Same class names, constructor arguments, `forward(in0, in1, retPerLayer=False, normalize=False)` and
+state_dict keys as the reference (`scaling_layer.shift`, `net.slice1.0.weight` ..., `lin0.model.1.weight`
+... and the same under `lins.N.`), so the reference's weights/v0.1/vgg.pth loads with
+`load_state_dict(..., strict=False)` as it does there.  The forward runs HIP kernels only:
+  * `vst_lpips_input`: `2 x - 1` / im2tensor and the ScalingLayer, both inputs into one [2N,3,H,W] batch;
+  * the VGG16 trunk (torchvision features[0:30]) once over that batch, on the convolution and pooling
+    kernels `vst.reconet.network.Vgg16` runs (GEMM scope "lpips");
+  * `vst_lpips_head` per level: both normalisations, the squared difference, the 1x1 linear layer (or
+    the channel sum of `lpips=False`) and the spatial mean in one pass over the two feature halves,
+    the five levels summed by the kernel's accumulate flag; `spatial=True` upsamples the per-level maps
+    with `ops.resize_bilinear(..., addend=...)`.
+Forward only, as the reference evaluates (`eval_mode`): inputs that require grad, `pnet_tune=True` and
+trunks other than VGG16 raise `VstError`.  Nothing synchronises with the host.
+
+Weights.  The trunk takes `weights=`, a path to a local torchvision vgg16 state dict (the reference
+downloads IMAGENET1K_V1), else torchvision's default init.  The learned linear layers (1,472 floats)
+are not shipped: `model_path=None` looks for weights/v0.1/vgg.pth beside the `lpips` drop-in package
+(video-style-transfer_amd/adaattn/lpips/); copy the reference's AA/lpips/weights/v0.1/vgg.pth there.
+"""
+import os
+from collections import namedtuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from .. import ops
+from .._lib import VstError, lib, ptr, stream
+from ..reconet.network import _load_torchvision_features, run_vgg_slice, vgg_features
+
+__all__ = ["LPIPS", "ScalingLayer", "NetLinLayer", "vgg16", "normalize_tensor", "spatial_average", "upsample",
+           "im2tensor", "load_image"]
+
+# torchvision VGG16 "D" features[0:30]
+_VGG16_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512]
+VggOutputs = namedtuple("VggOutputs", ["relu1_2", "relu2_2", "relu3_3", "relu4_3", "relu5_3"])
+# where `model_path=None` looks for the linear layers: beside the `lpips` drop-in package
+DROPIN_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "adaattn", "lpips")
+MIN_SIDE = 16  # four 2x2 pools
+# the ScalingLayer's per-channel constants (AA/lpips/lpips.py:167-168; vst_lpips_input carries the same)
+SHIFT, SCALE = (-0.030, -0.088, -0.188), (0.458, 0.448, 0.450)
+
+
+def default_model_path(version="0.1", net="vgg"):
+    return os.path.join(DROPIN_DIR, "weights", "v%s" % version, "%s.pth" % net)
+
+
+# ------------------------------------------------------------------------------------------------
+# functions of AA/lpips/__init__.py and AA/lpips/lpips.py
+def normalize_tensor(in_feat, eps=1e-10):
+    """AA/lpips/__init__.py:13-15: in_feat / (sqrt(sum over channels of in_feat^2) + eps)."""
+    x = ops._check(in_feat, "normalize_tensor", 4)
+    N, C, H, W = x.shape
+    P = H * W
+    # existing entries only: the channel norm, + eps, its reciprocal, and the product with every channel
+    den, e = torch.empty((N, P), device=x.device), torch.empty((N, P), device=x.device)
+    lib.vst_channel_norm(ptr(x), ptr(den), N, C, P, stream())
+    lib.vst_fill(ptr(e), N * P, float(eps), stream())
+    lib.vst_sum4(ptr(den), ptr(e), None, None, ptr(den), N * P, stream())
+    lib.vst_reciprocal(ptr(den), ptr(e), N * P, stream())
+    out = torch.empty_like(x)
+    lib.vst_outer_axpy(ptr(x), None, None, ptr(e), 0.0, ptr(out), N, C, P, stream())
+    return out
+
+
+def spatial_average(in_tens, keepdim=True):
+    """AA/lpips/lpips.py:14-15: the mean over H and W."""
+    x = ops._check(in_tens, "spatial_average", 4)
+    N, C, H, W = x.shape
+    if H * W == 1:
+        mean = x.reshape(N * C).clone()
+    else:
+        mean, std = torch.empty(N * C, device=x.device), torch.empty(N * C, device=x.device)
+        lib.vst_plane_meanstd(ptr(x), ptr(mean), ptr(std), N * C, H * W, stream())
+    return mean.view(N, C, 1, 1) if keepdim else mean.view(N, C)
+
+
+def upsample(in_tens, out_HW=(64, 64)):
+    """AA/lpips/lpips.py:18-20: bilinear, align_corners=False."""
+    return ops.resize_bilinear(in_tens, tuple(int(v) for v in out_HW))
+
+
+def im2tensor(image, imtype=np.uint8, cent=1.0, factor=255.0 / 2.0):
+    """AA/lpips/__init__.py:86-88: an (H,W,3) array -> the (1,3,H,W) host tensor image / factor - cent
+    (float64, then fp32).  `LPIPS.forward_u8` does this on the device from the uint8 frame."""
+    planes = np.asarray(image).astype(np.float64) / factor - cent
+    return torch.from_numpy(np.ascontiguousarray(planes.transpose(2, 0, 1)[None]).astype(np.float32))
+
+
+def load_image(path):
+    """AA/lpips/__init__.py:67-79 for the raster formats: (H,W,3) uint8 RGB."""
+    from ..metrics import imread  # noqa: PLC0415
+
+    return imread(path)[:, :, ::-1]
+
+
+# ------------------------------------------------------------------------------------------------
+def _input(src, out, offset, N, H, W, u8, swap_rb, normalize, scaling):
+    p = ops._ptr_u8(src, "frames") if u8 else ptr(src)
+    lib.vst_lpips_input(p, int(u8), ptr(out), offset, N, H, W, int(swap_rb), int(normalize), int(scaling), stream())
+
+
+class ScalingLayer(nn.Module):
+    """AA/lpips/lpips.py:164-171: (inp - shift) / scale.  The buffers are the reference's (state_dict
+    parity); the kernel carries the same constants."""
+
+    def __init__(self):
+        super().__init__()
+        for name, values in (("shift", SHIFT), ("scale", SCALE)):
+            self.register_buffer(name, torch.tensor(values, dtype=torch.float32).view(1, 3, 1, 1))
+
+    def forward(self, inp):
+        x = ops._check(inp, "ScalingLayer input", 4)
+        if x.shape[1] != 3:
+            raise VstError(f"ScalingLayer: expected 3 channels, got {x.shape[1]}")
+        out = torch.empty_like(x)
+        _input(x, out, 0, x.shape[0], x.shape[2], x.shape[3], False, False, False, True)
+        return out
+
+
+class NetLinLayer(nn.Module):
+    """AA/lpips/lpips.py:174-193: the parameter container of one level's 1x1 conv (Dropout first when
+    `use_dropout`, so the weight is `model.1.weight` as in the reference's files).  Inside `LPIPS` the
+    conv is part of `vst_lpips_head`; called on its own it is a 1x1 convolution."""
+
+    def __init__(self, chn_in, chn_out=1, use_dropout=False):
+        super().__init__()
+        mods = [nn.Conv2d(chn_in, chn_out, kernel_size=1, bias=False)]
+        if use_dropout:
+            mods.insert(0, nn.Dropout())  # never applied (eval only); it puts the conv at index 1
+        self.model = nn.Sequential(*mods)
+
+    @property
+    def weight(self):
+        return self.model[-1].weight
+
+    def forward(self, x):
+        if self.training and len(self.model) > 1:
+            raise VstError("NetLinLayer: forward only (eval mode); dropout training is not carried")
+        with torch.no_grad():
+            return ops.conv2d(x, self.weight.detach(), None, stride=1, pad=0)
+
+
+class vgg16(nn.Module):
+    """AA/lpips/pretrained_networks.py:98-136: torchvision vgg16 features[0:30] in five slices; forward
+    returns relu1_2 .. relu5_3.  `weights`: a local torchvision vgg16 state dict (no download)."""
+
+    def __init__(self, requires_grad=False, pretrained=True, weights=None):
+        super().__init__()
+        if requires_grad:
+            raise VstError("lpips: the trunk is forward only (pnet_tune / requires_grad is not carried)")
+        feats = vgg_features(_VGG16_CFG, 30)
+        _load_torchvision_features(feats, weights)
+        self.N_slices = 5
+        for s, (lo, hi) in enumerate(((0, 4), (4, 9), (9, 16), (16, 23), (23, 30))):
+            seq = nn.Sequential()
+            for x in range(lo, hi):
+                seq.add_module(str(x), feats[x])
+            setattr(self, f"slice{s + 1}", seq)
+        for p in self.parameters():
+            p.requires_grad = False
+
+    def forward(self, X):
+        outs, h = [], X
+        with torch.no_grad(), ops.gemm_scope("lpips"):
+            for s in range(self.N_slices):
+                h = run_vgg_slice(getattr(self, f"slice{s + 1}"), h)  # slices 2..5 start with their own pool
+                outs.append(h)
+        return VggOutputs(*outs)
+
+
+class LPIPS(nn.Module):
+    """AA/lpips/lpips.py:24-161 for net="vgg" / "vgg16"."""
+
+    def __init__(self, pretrained=True, net="alex", version="0.1", lpips=True, spatial=False, pnet_rand=False,
+                 pnet_tune=False, use_dropout=True, model_path=None, eval_mode=True, verbose=True, weights=None):
+        super().__init__()
+        if net not in ("vgg", "vgg16"):
+            raise VstError(f"lpips: trunk {net!r} is not carried, only 'vgg' / 'vgg16': AlexNet and SqueezeNet need "
+                           "11x11 stride-4 convolutions and 3x3 stride-2 max-pools, which this library does not have")
+        if pnet_tune:
+            raise VstError("lpips: pnet_tune=True is not carried (forward only, as the reference evaluates)")
+        if verbose:
+            print(f"lpips: {'learned linear layers' if lpips else 'plain channel sum'} over the {net} trunk, "
+                  f"version {version}, {'per-pixel map' if spatial else 'one distance per pair'}")
+        self.pnet_type = net
+        self.pnet_tune = pnet_tune
+        self.pnet_rand = pnet_rand
+        self.spatial = spatial
+        self.lpips = lpips
+        self.version = version
+        self.scaling_layer = ScalingLayer()
+        self.chns = [64, 128, 256, 512, 512]
+        self.L = len(self.chns)
+        self.net = vgg16(pretrained=not self.pnet_rand, requires_grad=self.pnet_tune, weights=weights)
+        if lpips:
+            for k in range(self.L):
+                setattr(self, f"lin{k}", NetLinLayer(self.chns[k], use_dropout=use_dropout))
+            self.lins = nn.ModuleList([getattr(self, f"lin{k}") for k in range(self.L)])
+            if pretrained:
+                if model_path is None:
+                    model_path = default_model_path(version, net)
+                if not os.path.isfile(model_path):
+                    raise VstError(f"lpips: the linear-layer weights {model_path} are missing; this repository does "
+                                   "not ship them: copy the reference's lpips/weights/v%s/vgg.pth there, pass "
+                                   "model_path=, or build with pretrained=False" % version)
+                if verbose:
+                    print(f"lpips: linear layers from {model_path}")
+                self.load_state_dict(torch.load(model_path, map_location="cpu", weights_only=True), strict=False)
+        if eval_mode:
+            self.eval()
+
+    # -- inputs ----------------------------------------------------------------------------------
+    def _batch(self, N, H, W, like):
+        if H < MIN_SIDE or W < MIN_SIDE:
+            raise VstError(f"lpips: images must be at least {MIN_SIDE} x {MIN_SIDE} (four 2x2 pools), got {H} x {W}")
+        return torch.empty((2 * N, 3, H, W), dtype=torch.float32, device=like.device)
+
+    def forward(self, in0, in1, retPerLayer=False, normalize=False):
+        """in0, in1: (N,3,H,W) fp32 device tensors in [-1,1] (`normalize=True`: in [0,1]).  Returns the
+        (N,1,1,1) distances ((N,1,H,W) with spatial=True); retPerLayer: (value, [the five levels])."""
+        if in0.requires_grad or in1.requires_grad:
+            raise VstError("lpips: forward only -- inputs that require grad are not carried")
+        a, b = ops._check(in0, "in0", 4), ops._check(in1, "in1", 4)
+        if a.shape != b.shape or a.shape[1] != 3:
+            raise VstError(f"lpips: inputs must be two (N,3,H,W) tensors of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+        N, _, H, W = a.shape
+        x = self._batch(N, H, W, a)
+        for half, t in enumerate((a, b)):
+            _input(t, x, half * N, N, H, W, False, False, normalize, self.version == "0.1")
+        return self._distance(x, N, H, W, retPerLayer)
+
+    def forward_u8(self, img0_u8, img1_u8, bgr=True, retPerLayer=False):
+        """The same from (N,H,W,3) uint8 device frames (bgr: cv2's channel order): im2tensor and the
+        ScalingLayer in one pass (`lpips_loss`, AA/eval.py:26-30, without the host round trip)."""
+        for t in (img0_u8, img1_u8):
+            if t.dim() != 4 or t.shape[-1] != 3:
+                raise VstError(f"lpips: frames must be (N,H,W,3) uint8, got {tuple(t.shape)}")
+        if img0_u8.shape != img1_u8.shape:
+            raise VstError(f"lpips: frames {tuple(img0_u8.shape)} and {tuple(img1_u8.shape)} differ")
+        N, H, W, _ = img0_u8.shape
+        ops._ptr_u8(img0_u8, "img0"), ops._ptr_u8(img1_u8, "img1")
+        x = self._batch(N, H, W, img0_u8)
+        for half, t in enumerate((img0_u8, img1_u8)):
+            _input(t, x, half * N, N, H, W, True, bgr, False, self.version == "0.1")
+        return self._distance(x, N, H, W, retPerLayer)
+
+    # -- trunk + heads ---------------------------------------------------------------------------
+    def _distance(self, x, N, H, W, retPerLayer):
+        feats = self.net(x)
+        dev = x.device
+        total = torch.empty(N, dtype=torch.float32, device=dev)
+        layers, maps = [], []
+        for k, f in enumerate(feats):
+            C, h, w = f.shape[1:]
+            P = h * w
+            wk = self.lins[k].weight.detach().reshape(-1) if self.lpips else None
+            layer = torch.empty(N, dtype=torch.float32, device=dev)
+            dmap = torch.empty((N, 1, h, w), dtype=torch.float32, device=dev) if self.spatial else None
+            ws = torch.empty(max(1, lib.vst_lpips_head_workspace(N, C, P) // 8), dtype=torch.float64, device=dev)
+            lib.vst_lpips_head(ptr(f), C * P, ptr(f) + 4 * N * C * P, C * P, ptr(wk), N, C, P, ptr(layer), ptr(total),
+                               int(k > 0), ptr(dmap), ws.data_ptr(), stream())
+            layers.append(layer)
+            maps.append(dmap)
+        if self.spatial:
+            val = None
+            for m in maps:  # the five upsampled maps summed by the resize's addend, in level order
+                val = ops.resize_bilinear(m, (H, W), addend=val)
+            res = [ops.resize_bilinear(m, (H, W)) for m in maps] if retPerLayer else None
+        else:
+            val = total.view(N, 1, 1, 1)
+            res = [v.view(N, 1, 1, 1) for v in layers]
+        return (val, res) if retPerLayer else val

@@ -1,9 +1,9 @@
 """Evaluation metrics on the MI355X: the temporal (warping) error of RT/utilities.py:194-240 and
-AA/exps_sintel.py:66-110, and SSIM / Gram distance / histogram KL of AA/eval.py, on the HIP kernels
-of csrc/metrics.hip.  As everywhere in this package there is no CPU path: tensors on the host raise
+AA/exps_sintel.py:66-110, and SSIM / Gram distance / histogram KL / LPIPS of AA/eval.py, on the HIP
+kernels of csrc/metrics.hip and csrc/lpips.hip (the LPIPS model itself is vst.lpips).  As everywhere in this package there is no CPU path: tensors on the host raise
 `VstError`.
 
-Out of scope: LPIPS and SIFID (their trunks' weights are a download), RAFT flow
+Out of scope: SIFID (an InceptionV3 trunk whose weights are a download), RAFT flow
 estimation, and the three grey-level histogram metrics of AA/eval.py:111-164 (OpenCV's BGR2GRAY
 cannot be pinned without OpenCV).
 """
@@ -176,6 +176,58 @@ def gram_distance(vgg19, img, style):
         terms = [ops.mse(ops.gram_matrix(fcs[k], per_hw=True), ops.gram_matrix(fs[k], per_hw=True),
                          1.0 / len(GRAM_FEATURES)) for k in GRAM_FEATURES]
         return ops.sum_scalars(*terms)
+
+
+# ------------------------------------------------------------------------------------------------
+# LPIPS
+def lpips_distance(model, img0_u8, img1_u8, bgr=True):
+    """AA/eval.py:26-30 / AA/exps_image.py's lpips columns on N pairs at once: (N,H,W,3) uint8 device
+    frames (bgr: cv2's order) -> the (N,) distances of `model` (a vst.lpips.LPIPS), no host sync."""
+    return model.forward_u8(img0_u8, img1_u8, bgr=bgr).reshape(-1)
+
+
+class LPIPSMean:
+    """The mean LPIPS distance over a folder of pairs, accumulated on the device: `update` adds the
+    distances of its N pairs to a device accumulator (vst_sum_scaled, vst_sum4) and N to the pair count;
+    nothing synchronises until `result()`.  The accumulator is fp32 (the library's sum entries are),
+    unlike TemporalError's fp64 one: each update adds about 2^-24 relative, which is fine for folders of
+    thousands of pairs and not meant for millions.  The model must give one distance per pair
+    (spatial=False)."""
+
+    def __init__(self, model, bgr=True):
+        self.model, self.bgr = model, bool(bgr)
+        self.reset()
+
+    def reset(self):
+        self._acc, self._pairs = None, 0
+
+    def update(self, img0_u8, img1_u8):
+        if getattr(self.model, "spatial", False):
+            raise VstError("LPIPSMean: the model must return one distance per pair (spatial=False)")
+        d = lpips_distance(self.model, img0_u8, img1_u8, bgr=self.bgr)
+        if d.numel() != img0_u8.shape[0]:
+            raise VstError(f"LPIPSMean: {d.numel()} distances for {img0_u8.shape[0]} pairs")
+        if self._acc is None:
+            self._acc = torch.zeros(1, dtype=torch.float32, device=d.device)
+        elif self._acc.device != d.device:
+            raise VstError("LPIPSMean: updates from different devices")
+        ws = torch.empty(ops.LOSS_WS, dtype=torch.float32, device=d.device)
+        part = torch.empty(3, dtype=torch.float32, device=d.device)
+        lib.vst_sum_scaled(ptr(d), d.numel(), 1.0, ptr(ws), ptr(part), stream())
+        ops.sum_into(self._acc, [self._acc, part[:1]])
+        self._pairs += d.numel()
+        return self
+
+    def state(self):
+        """(device sum (1,), pairs) (no sync)."""
+        if self._acc is None:
+            raise VstError("LPIPSMean: no update yet")
+        return self._acc, self._pairs
+
+    def result(self):
+        """The mean as a Python float: the one host synchronisation."""
+        acc, pairs = self.state()
+        return acc.item() / pairs
 
 
 # ------------------------------------------------------------------------------------------------
