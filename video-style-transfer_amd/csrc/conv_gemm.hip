@@ -346,90 +346,75 @@ static long apack_floats(int M, int K, int mode) {
   return vst_mode_arith(mode) == VST_GEMM_BF16X6 ? f * 3 / 2 : f;
 }
 
-// Halo-kernel plan of a conv GEMM launch (shared by the launch and vst_conv_splitk_workspace, so the
+// Halo-kernel plan of a conv GEMM call (shared by the launch and the workspace queries, so the
 // workspace a caller is told to supply is exactly what the launch will use): the halo block config
-// (0 = the per-tap kernel runs) and the split-K slice count S (1 = unsplit).
+// (0 = the per-tap kernel runs) and the split-K slice count S (1 = unsplit).  Reads the call's
+// geometry, epi, a_batch_stride and gmask fields; a query describes its call without a gather mask.
 struct HaloPlan {
   int hcfg, S, tiles, mpad;
 };
-static HaloPlan halo_plan(int N, int Cs, int M, int Ho, int Wo, int KH, int KW, int gmode, int stride, int pad,
-                          int pad_x, int up, int epi, long a_batch_stride, int mode, bool gmask_free = true) {
+static HaloPlan halo_plan(const ConvParams& P, int N, int mode) {
   HaloPlan hp{0, 1, 0, 0};
-  const int am = vst_mode_arith(mode);
+  const int am = vst_mode_arith(mode), KH = P.KH, KW = P.KW, gmode = P.gmode;
+  const bool gmask_free = P.gmask == nullptr;
   // (the packed A carries vst_conv_pack_dims' Mpad; the halo block's M tile must divide it)
-  const int pack_bm = cfg_bm(select_cfg(M));
-  hp.mpad = (M + pack_bm - 1) / pack_bm * pack_bm;
-  const int hcfg = halo_cfg(M, hp.mpad);
+  const int pack_bm = cfg_bm(select_cfg(P.M));
+  hp.mpad = (P.M + pack_bm - 1) / pack_bm * pack_bm;
+  const int hcfg = halo_cfg(P.M, hp.mpad);
   // 3x3 taps (stride 1, reflect / zero / transposed gathers), or the 2x2 phase-stacked GEMMs
   // (EPI_PHASE2: the stride-2 data gradient's transposed gather, the up2 forward's edge clamp)
-  const bool ph2 = (epi & EPI_PHASE2) != 0;
+  const bool ph2 = (P.epi & EPI_PHASE2) != 0;
   // 9 x 1 over a kw-unfolded operand (column pad 0): the 64- / 128-row block selections only
-  const bool k91 = !ph2 && KH == 9 && KW == 1 && pad_x == 0 && gmask_free && (hcfg == HALO_M64 || hcfg == HALO_M128) &&
+  const bool k91 = !ph2 && KH == 9 && KW == 1 && P.pad_x == 0 && gmask_free && (hcfg == HALO_M64 || hcfg == HALO_M128) &&
                    (gmode == GM_REFLECT || gmode == GM_TRANSPOSED);
   // 1 x 9 over the reflect-padded rows (ConvTanh's row-split forward: 27 rows in a 32-row pack)
-  const bool k19 = !ph2 && KH == 1 && KW == 9 && pad_x == pad && gmask_free && hp.mpad == 32 && gmode == GM_REFLECT &&
-                   epi == 0;
+  const bool k19 = !ph2 && KH == 1 && KW == 9 && P.pad_x == P.pad && gmask_free && hp.mpad == 32 &&
+                   gmode == GM_REFLECT && P.epi == 0;
   const int hcfg19 = k19 ? H1x4S : hcfg;
   const bool taps_ok = ph2 ? (KH == 2 && KW == 2 && (gmode == GM_TRANSPOSED || gmode == GM_CLAMP) && gmask_free)
                        : (k91 || k19) ? true
                              : (KH == 3 && KW == 3 && (gmode == GM_REFLECT || gmode == GM_ZERO || gmode == GM_TRANSPOSED));
   const bool halo = hcfg19 && !(mode & VST_GEMM_PERTAP) && (mode & VST_GEMM_KBLOCK) && taps_ok &&
-                    stride == 1 && up == 1 && Cs % 16 == 0 && (pad_x == pad || k91) && a_batch_stride == 0 &&
-                    !(epi & EPI_AFFINE) &&
+                    P.stride == 1 && P.up == 1 && P.Cs % 16 == 0 && (P.pad_x == P.pad || k91) &&
+                    P.a_batch_stride == 0 && !(P.epi & EPI_AFFINE) &&
                     (am == VST_GEMM_BF16X6 || am == VST_GEMM_BF16X3 || am == VST_GEMM_BF16 || am == VST_GEMM_F16);
   if (!halo) return hp;
   hp.hcfg = hcfg19;
   const int bm = 32 * halo_wm(hcfg19), th = 4 * halo_wn(hcfg19);
-  hp.tiles = ((Wo + HTW - 1) / HTW) * ((Ho + th - 1) / th);
+  hp.tiles = ((P.Wo + HTW - 1) / HTW) * ((P.Ho + th - 1) / th);
   // split-K when the grid is too small for the chip (AdaAttN config 4's decoder and VGG19 conv4 /
   // conv5 layers: 128-384 blocks); every split launch matches its unsplit launch to <= 3e-6
   // (tools/split_diag.py).  Not for the phase-stacked epilogue (the reduce writes plain / padded-grid
   // outputs only).
   if (!ph2 && !(mode & VST_GEMM_NOSPLIT))
-    hp.S = halo_ksplit((long)hp.tiles * (hp.mpad / bm) * N, Cs / 16);
+    hp.S = halo_ksplit((long)hp.tiles * (hp.mpad / bm) * N, P.Cs / 16);
   return hp;
 }
 
-// bytes of split-K workspace a planned launch needs (0: unsplit)
-static long splitk_bytes(const HaloPlan& hp, int N, int M, int Ho, int Wo) {
-  return hp.S > 1 ? (long)hp.S * N * M * Ho * Wo * (long)sizeof(float) : 0;
+// bytes of split-K workspace a planned call needs (0: unsplit, which every per-tap plan is)
+static long splitk_bytes(const HaloPlan& hp, const ConvParams& P, int N) {
+  return hp.S > 1 ? (long)hp.S * N * P.M * P.Ho * P.Wo * (long)sizeof(float) : 0;
 }
 
-static int conv_gemm_launch(const float* src, const float* wpack, const float* bias, const float* mask, float* out,
-                            int N, int Cs, int Hs, int Ws, int M, int K, int Ho, int Wo, int KH, int KW, int gmode,
-                            int stride, int pad, int pad_x, int up, int epi, long a_batch_stride, float* aux,
-                            const float* gmask, int mode, void* stream, const float* ep_ra = nullptr,
-                            const float* ep_rb = nullptr, const float* ep_rd = nullptr,
-                            const float* ep_cg = nullptr, float* ph_border = nullptr, int ph_H = 0, int ph_W = 0,
-                            int ph_pad = 0, void* workspace = nullptr, long ws_bytes = 0, bool reflect_t = false) {
-  ConvParams P;
-  P.ph_border = ph_border;
-  P.ph_H = ph_H;
-  P.ph_W = ph_W;
-  P.ph_pad = ph_pad;
-  P.src = src;
-  P.wpack = wpack;
-  P.bias = bias;
-  P.mask = mask;
-  P.gmask = gmask;
-  P.out = out;
-  P.aux = aux;
-  P.a_batch_stride = a_batch_stride;
-  P.Cs = Cs;
-  P.Hs = Hs;
-  P.Ws = Ws;
-  P.M = M;
-  int cfg = widen_cfg(select_cfg(M), (long)Ho * Wo);
+// P: the call as its entry point describes it (operands, geometry, epilogue); the rest is derived here
+static int conv_gemm_launch(ConvParams P, int N, int mode, void* stream, void* workspace = nullptr,
+                            long ws_bytes = 0, bool reflect_t = false) {
+  const int M = P.M, am = vst_mode_arith(mode);
+  P.Kpad = (P.K + BK - 1) / BK * BK;
+  P.fd_Wo = make_fastdiv(P.Wo);
+  P.fd_Cs = make_fastdiv(P.Cs);
+  P.fd_KW = make_fastdiv(P.KW);
+  P.kb = (mode & VST_GEMM_KBLOCK) ? 1 : 0;
+  int cfg = widen_cfg(select_cfg(M), (long)P.Ho * P.Wo);
   {
     // 256-row tiles for 256-multiple M on the single-product paths (then A-direct below).  Not under
     // bf16x3: its 256 x 128 LDS-A tile spills 63 VGPRs (eight accumulator fragments and two pieces per
     // operand); the 128-row tile ran config 5 at 128.4 / 128.1 ms against 128.5 / 129.6 (A/B/A/B on one
     // box, the AdaAttN attention projections)
-    const int am = vst_mode_arith(mode);
     if (cfg == T128 && M % 256 == 0 && (am == VST_GEMM_BF16 || am == VST_GEMM_F16)) cfg = T256;
     // bf16x6 A-direct blocks: 64-, 128- and 256-row tiles always, the 192-row tile for data
     // gradients only (its forward keeps the LDS-A tile: DESIGN.md §4.2 item 3)
-    const bool dg = gmode == GM_TRANSPOSED;
+    const bool dg = P.gmode == GM_TRANSPOSED;
     if (am == VST_GEMM_BF16X6) {
       if (cfg == T128 && M % 256 == 0) cfg = T256A;
       if (cfg == T128) cfg = T128A;
@@ -446,54 +431,36 @@ static int conv_gemm_launch(const float* src, const float* wpack, const float* b
       if (cfg == T192) cfg = T192A;
     }
   }
+  hipStream_t st = (hipStream_t)stream;
+  const bool gm = P.gmask != nullptr;
   // 3x3 stride-1 convs in the channel-blocked K order: the halo-tiled kernel (conv_halo_kernel.h),
   // one A-direct wave per 32 weight rows -- 2 / 4 / 6 / 8 waves as the per-tap kernel's blocks
-  const int am = vst_mode_arith(mode);
-  const HaloPlan hp =
-      halo_plan(N, Cs, M, Ho, Wo, KH, KW, gmode, stride, pad, pad_x, up, epi, a_batch_stride, mode, gmask == nullptr);
+  const HaloPlan hp = halo_plan(P, N, mode);
   if (hp.hcfg) {
+    // stride, up, ep_* and kb stay as the call set them: halo_plan admits the call only with
+    // stride == 1, up == 1, no EPI_AFFINE (the one epilogue with ep_* operands) and VST_GEMM_KBLOCK
+    // set, which are the values this kernel is written for
     const int hcfg = hp.hcfg, bm = 32 * halo_wm(hcfg);
     P.Mpad = hp.mpad;
-    P.K = K;
-    P.Kpad = (K + BK - 1) / BK * BK;
-    P.Ho = Ho;
-    P.Wo = Wo;
-    P.KH = KH;
-    P.KW = KW;
-    P.gmode = gmode;
-    P.stride = 1;
-    P.pad = pad;
-    P.pad_x = pad_x;
-    P.up = 1;
-    P.epi = epi;
-    P.ep_ra = P.ep_rb = P.ep_rd = P.ep_cg = nullptr;
-    P.fd_Wo = make_fastdiv(Wo);
-    P.fd_Cs = make_fastdiv(Cs);
-    P.fd_KW = make_fastdiv(KW);
-    P.kb = 1;
-    hipStream_t st = (hipStream_t)stream;
     // the split's slices go to the caller's workspace (vst_conv_splitk_workspace bytes); a launch
     // given less runs unsplit -- same result up to fp32 summation order
-    const long need = splitk_bytes(hp, N, M, Ho, Wo);
-    int S = 1;
+    const long need = splitk_bytes(hp, P, N);
     if (need > 0 && workspace && ws_bytes >= need && ((uintptr_t)workspace & 15) == 0) {
-      S = hp.S;
       P.part = (float*)workspace;
-      P.ksplit = S;
+      P.ksplit = hp.S;
     }
-    dim3 grid(hp.tiles, P.Mpad / bm, N * S);
-    const bool gm = gmask != nullptr;
+    dim3 grid(hp.tiles, P.Mpad / bm, N * P.ksplit);
     if (reflect_t) {  // the reflect-pad data gradient on the exact grid (conv_halo_kernel RT)
       if (am == VST_GEMM_BF16X6) launch_halo_rt<3>(hcfg, grid, st, P);
       else if (am == VST_GEMM_F16) launch_halo_rt<4>(hcfg, grid, st, P);
       else if (am == VST_GEMM_BF16X3) launch_halo_rt<1>(hcfg, grid, st, P);
       else launch_halo_rt<2>(hcfg, grid, st, P);
-    } else if (am == VST_GEMM_BF16X6) launch_halo_prec<3>(gm, hcfg, KH, grid, st, P);
-    else if (am == VST_GEMM_F16) launch_halo_prec<4>(gm, hcfg, KH, grid, st, P);
-    else if (am == VST_GEMM_BF16X3) launch_halo_prec<1>(gm, hcfg, KH, grid, st, P);
-    else launch_halo_prec<2>(gm, hcfg, KH, grid, st, P);
-    if (S > 1) {
-      const int HWo = Ho * Wo;
+    } else if (am == VST_GEMM_BF16X6) launch_halo_prec<3>(gm, hcfg, P.KH, grid, st, P);
+    else if (am == VST_GEMM_F16) launch_halo_prec<4>(gm, hcfg, P.KH, grid, st, P);
+    else if (am == VST_GEMM_BF16X3) launch_halo_prec<1>(gm, hcfg, P.KH, grid, st, P);
+    else launch_halo_prec<2>(gm, hcfg, P.KH, grid, st, P);
+    if (P.ksplit > 1) {
+      const int HWo = P.Ho * P.Wo;
       dim3 rgrid((HWo + 1023) / 1024, N * M);
       if (HWo % 4 == 0) splitk_reduce_kernel<true><<<rgrid, 256, 0, st>>>(P, N);
       else splitk_reduce_kernel<false><<<rgrid, 256, 0, st>>>(P, N);
@@ -501,32 +468,11 @@ static int conv_gemm_launch(const float* src, const float* wpack, const float* b
     return vst_launch_status();
   }
   if (reflect_t) return VST_EUNSUPPORTED;  // (the halo kernel only: vst_conv_dgrad_reflect3_workspace says when)
-  int bm = cfg_bm(cfg), bn = cfg_bn(cfg);
+  const int bm = cfg_bm(cfg), bn = cfg_bn(cfg);
   P.Mpad = (M + bm - 1) / bm * bm;
-  P.K = K;
-  P.Kpad = (K + BK - 1) / BK * BK;
-  P.Ho = Ho;
-  P.Wo = Wo;
-  P.KH = KH;
-  P.KW = KW;
-  P.gmode = gmode;
-  P.stride = stride;
-  P.pad = pad;
-  P.pad_x = pad_x;
-  P.up = up;
-  P.epi = epi;
-  P.ep_ra = ep_ra;
-  P.ep_rb = ep_rb;
-  P.ep_rd = ep_rd;
-  P.ep_cg = ep_cg;
-  P.fd_Wo = make_fastdiv(Wo);
-  P.fd_Cs = make_fastdiv(Cs);
-  P.fd_KW = make_fastdiv(KW);
-  P.kb = (mode & VST_GEMM_KBLOCK) ? 1 : 0;
-  dim3 grid(ceil_div((long)Ho * Wo, bn), P.Mpad / bm, N);
-  const bool cfast = (Cs % 16) == 0, gm = gmask != nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  switch (vst_mode_arith(mode)) {
+  dim3 grid(ceil_div((long)P.Ho * P.Wo, bn), P.Mpad / bm, N);
+  const bool cfast = (P.Cs % 16) == 0;
+  switch (am) {
     case VST_GEMM_F32: launch_prec<0>(cfast, gm, cfg, grid, st, P); break;
     case VST_GEMM_BF16: launch_prec<2>(cfast, gm, cfg, grid, st, P); break;
     case VST_GEMM_BF16X6: launch_prec<3>(cfast, gm, cfg, grid, st, P); break;
@@ -661,8 +607,11 @@ int vst_conv_gemm(const float* src, const float* wpack, const float* bias, const
 long vst_conv_splitk_workspace(int N, int Cs, int M, int Ho, int Wo, int KH, int KW, int gmode, int stride, int pad,
                                int pad_x, int up, int epi, long a_batch_stride, int mode) {
   if (!vst_mode_ok(mode) || N <= 0 || Cs <= 0 || M <= 0 || Ho <= 0 || Wo <= 0) return 0;
-  const HaloPlan hp = halo_plan(N, Cs, M, Ho, Wo, KH, KW, gmode, stride, pad, pad_x, up, epi, a_batch_stride, mode);
-  return hp.hcfg ? splitk_bytes(hp, N, M, Ho, Wo) : 0;
+  ConvParams P;
+  P.Cs = Cs, P.M = M, P.Ho = Ho, P.Wo = Wo;
+  P.KH = KH, P.KW = KW, P.gmode = gmode, P.stride = stride, P.pad = pad, P.pad_x = pad_x, P.up = up;
+  P.epi = epi, P.a_batch_stride = a_batch_stride;
+  return splitk_bytes(halo_plan(P, N, mode), P, N);
 }
 
 int vst_conv_gemm_padx(const float* src, const float* wpack, const float* bias, const float* mask, float* out, int N,
@@ -678,9 +627,12 @@ int vst_conv_gemm_padx(const float* src, const float* wpack, const float* bias, 
   if (gmode == GM_REFLECT) VST_CHECK_ARG(pad < Hs * up && pad_x < Ws * up);
   VST_CHECK_ARG(pad >= 0 && pad_x >= 0);
   VST_CHECK_ARG(a_batch_stride == 0 || a_batch_stride >= apack_floats(M, K, mode));
-  return conv_gemm_launch(src, wpack, bias, mask, out, N, Cs, Hs, Ws, M, K, Ho, Wo, KH, KW, gmode, stride, pad, pad_x,
-                          up, epi, a_batch_stride, aux, gmask, mode, stream, nullptr, nullptr, nullptr, nullptr,
-                          nullptr, 0, 0, 0, workspace, ws_bytes);
+  ConvParams P;
+  P.src = src, P.wpack = wpack, P.bias = bias, P.mask = mask, P.gmask = gmask, P.out = out, P.aux = aux;
+  P.Cs = Cs, P.Hs = Hs, P.Ws = Ws, P.M = M, P.K = K, P.Ho = Ho, P.Wo = Wo;
+  P.KH = KH, P.KW = KW, P.gmode = gmode, P.stride = stride, P.pad = pad, P.pad_x = pad_x, P.up = up;
+  P.epi = epi, P.a_batch_stride = a_batch_stride;
+  return conv_gemm_launch(P, N, mode, stream, workspace, ws_bytes);
 }
 
 // out[n][m][p] = (sum_k A[n][k][m] B[n][k][p] + ra[n][m]) * rb[n][m] * cg[n][p] + rd[n][m]
@@ -690,8 +642,12 @@ int vst_attn_gemm(const float* src, const float* apack, float* out, int N, int K
   VST_CHECK_ARG(vst_mode_ok(mode));
   VST_CHECK_ARG(src && apack && out && rb && cg && N > 0 && K > 0 && P > 0 && M > 0);
   VST_CHECK_ARG(a_batch_stride == 0 || a_batch_stride >= apack_floats(M, K, mode));
-  return conv_gemm_launch(src, apack, nullptr, nullptr, out, N, K, 1, P, M, K, 1, P, 1, 1, GM_ZERO, 1, 0, 0, 1,
-                          EPI_AFFINE, a_batch_stride, nullptr, nullptr, mode, stream, ra, rb, rd, cg);
+  ConvParams C;  // a 1x1 conv over the [K][1 x P] source
+  C.src = src, C.wpack = apack, C.out = out, C.a_batch_stride = a_batch_stride;
+  C.Cs = K, C.Hs = 1, C.Ws = P, C.M = M, C.K = K, C.Ho = 1, C.Wo = P;
+  C.KH = C.KW = 1, C.gmode = GM_ZERO, C.stride = 1, C.up = 1;
+  C.epi = EPI_AFFINE, C.ep_ra = ra, C.ep_rb = rb, C.ep_rd = rd, C.ep_cg = cg;
+  return conv_gemm_launch(C, N, mode, stream);
 }
 
 int vst_pack_weight_phase2(const float* w, float* packed, int Cout, int Cin, int KS, int Mpad, int Kpad,
@@ -711,10 +667,13 @@ int vst_conv_dgrad_s2(const float* dy, const float* wpack, const float* gmask, f
   VST_CHECK_ARG(dy && wpack && dx && border && N > 0 && Cout > 0 && Ho > 0 && Wo > 0 && Cin > 0 && KS > 0);
   VST_CHECK_ARG(pad >= 0 && pad < H && pad < W && Ho == (H + 2 * pad - KS) / 2 + 1 && Wo == (W + 2 * pad - KS) / 2 + 1);
   const int K2 = (KS + 1) / 2;
-  const int Hc = (H + 2 * pad + 1) / 2, Wc = (W + 2 * pad + 1) / 2;
-  return conv_gemm_launch(dy, wpack, nullptr, nullptr, dx, N, Cout, Ho, Wo, 4 * Cin, K2 * K2 * Cout, Hc, Wc, K2, K2,
-                          GM_TRANSPOSED, 1, 0, 0, 1, EPI_PHASE2, 0, nullptr, gmask, mode, stream, nullptr, nullptr, nullptr,
-                          nullptr, border, H, W, pad);
+  ConvParams P;  // a K2 x K2 transposed gather of dY onto the phase grid
+  P.src = dy, P.wpack = wpack, P.gmask = gmask, P.out = dx;
+  P.Cs = Cout, P.Hs = Ho, P.Ws = Wo, P.M = 4 * Cin, P.K = K2 * K2 * Cout;
+  P.Ho = (H + 2 * pad + 1) / 2, P.Wo = (W + 2 * pad + 1) / 2;
+  P.KH = P.KW = K2, P.gmode = GM_TRANSPOSED, P.stride = 1, P.up = 1;
+  P.epi = EPI_PHASE2, P.ph_border = border, P.ph_H = H, P.ph_W = W, P.ph_pad = pad;
+  return conv_gemm_launch(P, N, mode, stream);
 }
 
 // Forward of nearest-x2 upsample -> ReflectionPad2d(1) -> Conv2d(k3, stride 1) (UpsampleConvLayer,
@@ -754,9 +713,12 @@ int vst_conv_up2_fwd(const float* x, const float* wpack, const float* bias, floa
                      int Cout, int mode, void* stream) {
   VST_CHECK_ARG(vst_mode_ok(mode));
   VST_CHECK_ARG(x && wpack && out && N > 0 && Cin > 0 && H > 0 && W > 0 && Cout > 0);
-  return conv_gemm_launch(x, wpack, bias, nullptr, out, N, Cin, H, W, 4 * Cout, 4 * Cin, H + 1, W + 1, 2, 2, GM_CLAMP,
-                          1, 1, 1, 1, EPI_PHASE2 | (bias ? EPI_BIAS : 0), 0, nullptr, nullptr, mode, stream, nullptr,
-                          nullptr, nullptr, nullptr, nullptr, 2 * H, 2 * W, 1);
+  ConvParams P;
+  P.src = x, P.wpack = wpack, P.bias = bias, P.out = out;
+  P.Cs = Cin, P.Hs = H, P.Ws = W, P.M = 4 * Cout, P.K = 4 * Cin, P.Ho = H + 1, P.Wo = W + 1;
+  P.KH = P.KW = 2, P.gmode = GM_CLAMP, P.stride = 1, P.pad = P.pad_x = 1, P.up = 1;
+  P.epi = EPI_PHASE2 | (bias ? EPI_BIAS : 0), P.ph_H = 2 * H, P.ph_W = 2 * W, P.ph_pad = 1;
+  return conv_gemm_launch(P, N, mode, stream);
 }
 
 int vst_conv_cin3_k3(const float* x, const float* w, const float* b, float* out, int N, int H, int W, int Cout,
@@ -815,9 +777,12 @@ int vst_conv_dgrad_padout_kwu(const float* dyu, const float* wpack, const float*
                 pad < W && Ho == H + 2 * pad - KS + 1);
   // dyu rows are Wu = Wp rounded up to 4 wide (vst_unfold_kw's float4 rows); the GEMM covers Wp columns
   const int Hp = H + 2 * pad, Wp = W + 2 * pad, Wu = (Wp + 3) / 4 * 4;
-  return conv_gemm_launch(dyu, wpack, nullptr, mask, dx, N, Cu, Ho, Wu, Cin, KS * Cu, Hp, Wp, KS, 1, GM_TRANSPOSED, 1,
-                          0, 0, 1, EPI_PADOUT | (mask ? EPI_MASK : 0), 0, nullptr, nullptr, mode, stream, nullptr,
-                          nullptr, nullptr, nullptr, border, H, W, pad);
+  ConvParams P;
+  P.src = dyu, P.wpack = wpack, P.mask = mask, P.out = dx;
+  P.Cs = Cu, P.Hs = Ho, P.Ws = Wu, P.M = Cin, P.K = KS * Cu, P.Ho = Hp, P.Wo = Wp;
+  P.KH = KS, P.KW = 1, P.gmode = GM_TRANSPOSED, P.stride = 1, P.up = 1;
+  P.epi = EPI_PADOUT | (mask ? EPI_MASK : 0), P.ph_border = border, P.ph_H = H, P.ph_W = W, P.ph_pad = pad;
+  return conv_gemm_launch(P, N, mode, stream);
 }
 
 int vst_conv_dgrad_padout(const float* dy, const float* wpack, const float* mask, float* dx, float* border, int N,
@@ -827,10 +792,12 @@ int vst_conv_dgrad_padout(const float* dy, const float* wpack, const float* mask
   VST_CHECK_ARG(ws_bytes >= 0 && (workspace || ws_bytes == 0));
   VST_CHECK_ARG(dy && wpack && dx && border && N > 0 && Cout > 0 && Cin > 0 && KS > 0 && pad >= 0 && pad < H &&
                 pad < W && Ho == H + 2 * pad - KS + 1 && Wo == W + 2 * pad - KS + 1);
-  return conv_gemm_launch(dy, wpack, nullptr, mask, dx, N, Cout, Ho, Wo, Cin, KS * KS * Cout, H + 2 * pad,
-                          W + 2 * pad, KS, KS, GM_TRANSPOSED, 1, 0, 0, 1, EPI_PADOUT | (mask ? EPI_MASK : 0), 0, nullptr,
-                          nullptr, mode, stream, nullptr, nullptr, nullptr, nullptr, border, H, W, pad, workspace,
-                          ws_bytes);
+  ConvParams P;
+  P.src = dy, P.wpack = wpack, P.mask = mask, P.out = dx;
+  P.Cs = Cout, P.Hs = Ho, P.Ws = Wo, P.M = Cin, P.K = KS * KS * Cout, P.Ho = H + 2 * pad, P.Wo = W + 2 * pad;
+  P.KH = P.KW = KS, P.gmode = GM_TRANSPOSED, P.stride = 1, P.up = 1;
+  P.epi = EPI_PADOUT | (mask ? EPI_MASK : 0), P.ph_border = border, P.ph_H = H, P.ph_W = W, P.ph_pad = pad;
+  return conv_gemm_launch(P, N, mode, stream, workspace, ws_bytes);
 }
 
 int vst_fold_border(const float* border, const float* mask, float* dx, long NC, int H, int W, int pad, void* stream) {
@@ -843,16 +810,26 @@ int vst_fold_border(const float* border, const float* mask, float* dx, long NC, 
   return vst_launch_status();
 }
 
-// the halo plan of the reflect-pad 3x3 data gradient on the exact grid (hcfg 0: the form does not apply)
-static HaloPlan dgrad_reflect3_plan(int N, int Cout, int Cin, int H, int W, bool masked, int mode) {
-  if (H < 2 || W < 2) return HaloPlan{0, 1, 0, 0};
-  return halo_plan(N, Cout, Cin, H, W, 3, 3, GM_TRANSPOSED, 1, 1, 1, 1, masked ? EPI_MASK : 0, 0, mode);
+// the reflect-pad 3x3 data gradient on the exact grid as a conv call (operands but the mask unset)
+static ConvParams dgrad_reflect3_call(int Cout, int Cin, int H, int W, const float* mask) {
+  ConvParams P;
+  P.mask = mask;
+  P.Cs = Cout, P.Hs = H, P.Ws = W, P.M = Cin, P.K = 9 * Cout, P.Ho = H, P.Wo = W;
+  P.KH = P.KW = 3, P.gmode = GM_TRANSPOSED, P.stride = 1, P.pad = P.pad_x = 1, P.up = 1;
+  P.epi = mask ? EPI_MASK : 0;
+  return P;
+}
+// its halo plan (hcfg 0: the form does not apply)
+static HaloPlan dgrad_reflect3_plan(const ConvParams& P, int N, int mode) {
+  if (P.Ho < 2 || P.Wo < 2) return HaloPlan{0, 1, 0, 0};
+  return halo_plan(P, N, mode);
 }
 
 long vst_conv_dgrad_reflect3_workspace(int N, int Cout, int Cin, int H, int W, int mode) {
   if (!vst_mode_ok(mode) || N <= 0 || Cout <= 0 || Cin <= 0 || H <= 0 || W <= 0) return -1;
-  const HaloPlan hp = dgrad_reflect3_plan(N, Cout, Cin, H, W, false, mode);
-  return hp.hcfg ? splitk_bytes(hp, N, Cin, H, W) : -1;
+  const ConvParams P = dgrad_reflect3_call(Cout, Cin, H, W, nullptr);
+  const HaloPlan hp = dgrad_reflect3_plan(P, N, mode);
+  return hp.hcfg ? splitk_bytes(hp, P, N) : -1;
 }
 
 int vst_conv_dgrad_reflect3(const float* dy, const float* wpack, const float* mask, float* dx, int N, int Cout,
@@ -860,10 +837,10 @@ int vst_conv_dgrad_reflect3(const float* dy, const float* wpack, const float* ma
   VST_CHECK_ARG(vst_mode_ok(mode));
   VST_CHECK_ARG(ws_bytes >= 0 && (workspace || ws_bytes == 0));
   VST_CHECK_ARG(dy && wpack && dx && N > 0 && Cout > 0 && Cin > 0 && H > 0 && W > 0);
-  if (!dgrad_reflect3_plan(N, Cout, Cin, H, W, mask != nullptr, mode).hcfg) return VST_EUNSUPPORTED;
-  return conv_gemm_launch(dy, wpack, nullptr, mask, dx, N, Cout, H, W, Cin, 9 * Cout, H, W, 3, 3, GM_TRANSPOSED, 1, 1,
-                          1, 1, mask ? EPI_MASK : 0, 0, nullptr, nullptr, mode, stream, nullptr, nullptr, nullptr,
-                          nullptr, nullptr, 0, 0, 0, workspace, ws_bytes, true);
+  ConvParams P = dgrad_reflect3_call(Cout, Cin, H, W, mask);
+  if (!dgrad_reflect3_plan(P, N, mode).hcfg) return VST_EUNSUPPORTED;
+  P.src = dy, P.wpack = wpack, P.out = dx;
+  return conv_gemm_launch(P, N, mode, stream, workspace, ws_bytes, true);
 }
 
 int vst_fold_reflect(const float* dpad, float* dx, long NC, int Hs, int Ws, int pad, int up, int accumulate,

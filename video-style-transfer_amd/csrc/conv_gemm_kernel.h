@@ -15,23 +15,25 @@ __device__ __forceinline__ f32x4 mk4(float a, float b, float c, float d) {
 constexpr int BK = 16;  // k-tile depth
 constexpr int NT = 256;
 
+// An entry point fills the operand and geometry fields by name and leaves what it does not use at
+// its default; the launch (conv_gemm.hip) derives Mpad, Kpad, fd_*, kb and the split-K fields.
 struct ConvParams {
-  const float* src;
-  const float* wpack;
-  const float* bias;
-  const float* mask;
-  const float* gmask;
-  float* out;
-  float* aux;
-  long a_batch_stride;
-  int Cs, Hs, Ws;
-  int M, Mpad, K, Kpad;
-  int Ho, Wo;
-  int KH, KW, gmode, stride, pad, up;
-  int pad_x;  // column padding (= pad except for the dgrad ring segments)
-  int epi;
+  const float* src = nullptr;
+  const float* wpack = nullptr;
+  const float* bias = nullptr;
+  const float* mask = nullptr;
+  const float* gmask = nullptr;
+  float* out = nullptr;
+  float* aux = nullptr;
+  long a_batch_stride = 0;
+  int Cs = 0, Hs = 0, Ws = 0;
+  int M = 0, Mpad = 0, K = 0, Kpad = 0;
+  int Ho = 0, Wo = 0;
+  int KH = 0, KW = 0, gmode = 0, stride = 0, pad = 0, up = 0;
+  int pad_x = 0;  // column padding (= pad except for the dgrad ring segments)
+  int epi = 0;
   // EPI_AFFINE: v = (acc + ra[n][m]) * rb[n][m] * cg[n][p] + rd[n][m]  (ra, rd optional)
-  const float *ep_ra, *ep_rb, *ep_rd, *ep_cg;
+  const float *ep_ra = nullptr, *ep_rb = nullptr, *ep_rd = nullptr, *ep_cg = nullptr;
   // EPI_PHASE2 (stride-2 data gradient, all four parity phases in one GEMM): row m = ci*4 + 2a + b,
   // pixel (I, J) of the phase grid -> padded-grid position (2I + a, 2J + b); interior positions go
   // straight to dx [N][M/4][ph_H][ph_W], the reflect-pad border to ph_border [N][M/4][Hp][Wp].
@@ -39,10 +41,10 @@ struct ConvParams {
   // border buffer: its out-of-range phase positions are dropped.)
   // EPI_PADOUT (stride-1 data gradient over the padded grid): row m = ci, pixel (u, v) of the
   // padded grid, same interior / border split.
-  float* ph_border;
-  int ph_H, ph_W, ph_pad;
-  FastDiv fd_Wo, fd_Cs, fd_KW;
-  int kb;  // channel-blocked K order (VST_GEMM_KBLOCK, vst_common.h kdecode)
+  float* ph_border = nullptr;
+  int ph_H = 0, ph_W = 0, ph_pad = 0;
+  FastDiv fd_Wo{}, fd_Cs{}, fd_KW{};
+  int kb = 0;  // channel-blocked K order (VST_GEMM_KBLOCK, vst_common.h kdecode)
   // split-K of the halo kernel (conv_halo_kernel.h): blockIdx.z = n * ksplit + s, slice s sums its
   // share of the 16-channel blocks into part[s][n][M][Ho Wo] (raw accumulators); the reduce kernel
   // adds the slices in order and applies the epilogue

@@ -904,7 +904,6 @@ static int wminw(int c) {  // resident blocks per CU of each configuration (its 
 // reduction traffic, i.e. fill the 256 CUs evenly without over-splitting.
 static int plan_splits(long tiles, int N, int HWo, int c, long Mpad, long Jpad) {
   const long slots = 256L * wminw(c);
-  const long ktiles = (HWo + BK - 1) / BK;
   const double t_tile = wminw(c) * 2.0 * wbm(c) * WBN * BK / 0.44e12;  // s per k-tile per block
   long maxs = (HWo + 2 * BK - 1) / (2 * BK);                        // >= 2 k-tiles per split
   if (maxs > 64) maxs = 64;
@@ -921,8 +920,43 @@ static int plan_splits(long tiles, int N, int HWo, int c, long Mpad, long Jpad) 
       best = S;
     }
   }
-  (void)ktiles;
   return best;
+}
+
+// Slab geometry and split of one weight-gradient GEMM out[M][J] over HWo pixels per image: the
+// workspace queries, the launch and the reduce kernels all read it from here, so the slab a caller
+// sizes is the slab the launch writes and the reduce reads.
+struct WgPlan {
+  int M, J;
+  int c;           // row tile (wsel)
+  int Mpad, Jpad;  // slab rows (whole row tiles) and columns (whole 128-column tiles)
+  int S;           // split-K slices per image
+  long floats(int N) const { return (long)N * S * Mpad * Jpad; }
+};
+static WgPlan wg_plan(int N, int M, long J, int HWo) {
+  WgPlan p;
+  p.M = M;
+  p.J = (int)J;
+  p.c = wsel(M);
+  p.Mpad = (M + wbm(p.c) - 1) / wbm(p.c) * wbm(p.c);
+  p.Jpad = (int)((J + WBN - 1) / WBN * WBN);
+  const int S = plan_splits((long)(p.Mpad / wbm(p.c)) * (p.Jpad / WBN), N, HWo, p.c, p.Mpad, p.Jpad);
+  const int maxs = (HWo + 2 * BK - 1) / (2 * BK);
+  p.S = S < maxs ? S : (maxs > 0 ? maxs : 1);
+  return p;
+}
+
+// How the GEMM's operands are gathered: B columns j = ((kh, kw), ci) from src [N][Cs][Hs][Ws] at the
+// taps of output pixel (oy, ox) of the Ho x Wo grid, A rows from a [N][M][Ho][Wo] (row-split, asplit:
+// m = co*asplit + kh reads a[co][oy-kh][ox], a has Ha rows).  The defaults are a plain 1x1 product.
+struct WgGather {
+  int Cs, Hs, Ws, Ho, Wo;
+  int KH = 1, KW = 1, gmode = 1, stride = 1, pad = 0, up = 1;
+  int asplit = 0, Ha = 0;
+};
+// the plan of a gathered GEMM: J and the pixel count come from the gather, nowhere else
+static WgPlan wg_plan(int N, int M, const WgGather& g) {
+  return wg_plan(N, M, (long)g.KH * g.KW * g.Cs, g.Ho * g.Wo);
 }
 
 template <int PR, int GMD, int KD, bool S1>
@@ -967,98 +1001,53 @@ static void launch_wg2(int c, dim3 g, int mode, hipStream_t st, const Wg2Params&
 
 // row-tiled kernel applies: output rows a multiple of 16 wide (plain or row-split A gather), and
 // every source offset within the 2^31 B buffer range
-static bool wg2_ok(int asplit, int Wo) {
-  (void)asplit;
-  return Wo % BK == 0;
+static bool wg2_ok(int Wo) { return Wo % BK == 0; }
+
+// the fields WgParams and Wg2Params share
+template <class PT>
+static PT wg_params(const WgPlan& p, const WgGather& g, const float* a, const float* src, float* slab) {
+  PT P;
+  P.a = a, P.src = src, P.slab = slab;
+  P.M = p.M, P.Mpad = p.Mpad, P.J = p.J, P.Jpad = p.Jpad;
+  P.Cs = g.Cs, P.Hs = g.Hs, P.Ws = g.Ws, P.Ho = g.Ho, P.Wo = g.Wo;
+  P.KH = g.KH, P.KW = g.KW, P.stride = g.stride, P.pad = g.pad, P.up = g.up;
+  P.S = p.S, P.chunk = ((g.Ho * g.Wo + p.S - 1) / p.S + BK - 1) / BK * BK;
+  P.asplit = g.asplit, P.Ha = g.Ha;
+  return P;
 }
 
-static int run_wg(const float* a, const float* src, float* slab, int N, int M, int Cs, int Hs, int Ws, int Ho, int Wo,
-                  int KH, int KW, int gmode, int stride, int pad, int up, int S, int asplit, int Ha, int mode,
+static int run_wg(const WgPlan& p, const WgGather& g, const float* a, const float* src, float* slab, int N, int mode,
                   hipStream_t st) {
-  if (wg2_ok(asplit, Wo)) {
-    Wg2Params Q;
-    Q.a = a;
-    Q.src = src;
-    Q.slab = slab;
-    Q.M = M;
-    const int c = wsel(M);
-    Q.Mpad = (M + wbm(c) - 1) / wbm(c) * wbm(c);
-    Q.J = KH * KW * Cs;
-    Q.Jpad = (Q.J + WBN - 1) / WBN * WBN;
-    Q.Cs = Cs;
-    Q.Hs = Hs;
-    Q.Ws = Ws;
-    Q.Ho = Ho;
-    Q.Wo = Wo;
-    Q.KH = KH;
-    Q.KW = KW;
-    Q.stride = stride;
-    Q.pad = pad;
-    Q.up = up;
-    Q.S = S;
-    Q.asplit = asplit;
-    Q.Ha = Ha;
-    Q.chunk = ((Ho * Wo + S - 1) / S + BK - 1) / BK * BK;
+  const int c = p.c;
+  if (wg2_ok(g.Wo)) {
+    const Wg2Params Q = wg_params<Wg2Params>(p, g, a, src, slab);
     // 64- / 96-row tiles over more than 128 columns: 256-column blocks when that pads J no further
     // (ReCoNet conv1 J = 243, conv2 J = 432): the dY rows are split once per 256 columns instead of
     // per 128, and each wave runs twice the MFMAs per k-tile.  Same Mpad / Jpad / split count, so
     // the slab layout and the workspace size do not change.
     int cw = c;
-    if ((c == W64 || c == W96) && Q.J > WBN && Q.Jpad % (2 * WBN) == 0) cw = c == W64 ? W64N : W96N;
+    if ((c == W64 || c == W96) && p.J > WBN && p.Jpad % (2 * WBN) == 0) cw = c == W64 ? W64N : W96N;
     // J <= 64 on a 64-row tile: one 64 x 64 block per M tile (the slab keeps its 128-column stride;
     // its columns >= J are never written nor read)
-    if (c == W64 && Q.J <= 64) cw = W64H;
-    dim3 g(cw == W64H ? 1 : Q.Jpad / (cw == c ? WBN : 2 * WBN), Q.Mpad / wbm(c), N * S);
-    if (gmode == 0) launch_wg2<0>(cw, g, mode, st, Q);
-    else if (gmode == 2) launch_wg2<2>(cw, g, mode, st, Q);
-    else launch_wg2<1>(cw, g, mode, st, Q);
+    if (c == W64 && p.J <= 64) cw = W64H;
+    dim3 grid(cw == W64H ? 1 : p.Jpad / (cw == c ? WBN : 2 * WBN), p.Mpad / wbm(c), N * p.S);
+    if (g.gmode == 0) launch_wg2<0>(cw, grid, mode, st, Q);
+    else if (g.gmode == 2) launch_wg2<2>(cw, grid, mode, st, Q);
+    else launch_wg2<1>(cw, grid, mode, st, Q);
     return vst_launch_status();
   }
-  WgParams P;
-  P.a = a;
-  P.src = src;
-  P.slab = slab;
-  P.M = M;
-  int c = wsel(M);
-  P.Mpad = (M + wbm(c) - 1) / wbm(c) * wbm(c);
-  P.J = KH * KW * Cs;
-  P.Jpad = (P.J + WBN - 1) / WBN * WBN;
-  P.Cs = Cs;
-  P.Hs = Hs;
-  P.Ws = Ws;
-  P.Ho = Ho;
-  P.Wo = Wo;
-  P.KH = KH;
-  P.KW = KW;
-  P.gmode = gmode;
-  P.stride = stride;
-  P.pad = pad;
-  P.pad_x = pad;
-  P.up = up;
-  P.S = S;
-  P.asplit = asplit;
-  P.Ha = Ha;
-  int HWo = Ho * Wo;
-  P.chunk = ((HWo + S - 1) / S + BK - 1) / BK * BK;
-  P.fd_Wo = make_fastdiv(Wo);
-  P.fd_Cs = make_fastdiv(Cs);
-  P.fd_KW = make_fastdiv(KW);
+  WgParams P = wg_params<WgParams>(p, g, a, src, slab);
+  P.gmode = g.gmode;
+  P.pad_x = g.pad;
+  P.fd_Wo = make_fastdiv(g.Wo);
+  P.fd_Cs = make_fastdiv(g.Cs);
+  P.fd_KW = make_fastdiv(g.KW);
   // tap-uniform column tiles when the channels fill whole 128-column tiles (VGG / AdaAttN decoder
   // widths; measured slower for the ReCoNet widths 48/96/192, whose padded tiles waste MFMAs)
-  const bool tap = !asplit && KH * KW > 1 && Cs % WBN == 0;
-  const int gxn = tap ? KH * KW * ((Cs + WBN - 1) / WBN) : P.Jpad / WBN;
-  dim3 g(gxn, P.Mpad / wbm(c), N * S);
-  launch_wg(c, tap, g, mode, st, P);
+  const bool tap = !g.asplit && g.KH * g.KW > 1 && g.Cs % WBN == 0;
+  const int gxn = tap ? g.KH * g.KW * ((g.Cs + WBN - 1) / WBN) : p.Jpad / WBN;
+  launch_wg(c, tap, dim3(gxn, p.Mpad / wbm(c), N * p.S), mode, st, P);
   return vst_launch_status();
-}
-
-static int splits_for(int N, int M, long J, int HWo) {
-  int c = wsel(M);
-  long Mpad = (M + wbm(c) - 1) / wbm(c) * wbm(c);
-  long Jpad = (J + WBN - 1) / WBN * WBN;
-  int S = plan_splits((Mpad / wbm(c)) * (Jpad / WBN), N, HWo, c, Mpad, Jpad);
-  const int maxs = (HWo + 2 * BK - 1) / (2 * BK);
-  return S < maxs ? S : (maxs > 0 ? maxs : 1);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1153,7 +1142,7 @@ extern "C" {
 // workspace floats of vst_conv_wgrad_up2: slab + the four phase planes of dY
 long vst_conv_wgrad_up2_workspace(int N, int Cin, int H, int W, int Cout) {
   const int M = 4 * Cout, J = 4 * Cin, Wp = up2_wp(W);
-  return vst_wgrad_workspace(N, M, J, (H + 1) * Wp) + (long)N * M * (H + 1) * Wp;
+  return wg_plan(N, M, J, (H + 1) * Wp).floats(N) + (long)N * M * (H + 1) * Wp;
 }
 
 // dW of nearest-x2 upsample + reflect pad 1 + 3x3 conv; dy [N][Cout][2H][2W], x [N][Cin][H][W]
@@ -1161,40 +1150,35 @@ int vst_conv_wgrad_up2(const float* dy, const float* x, float* dw, float* worksp
                        int Cout, int accumulate, int mode, void* stream) {
   VST_CHECK_ARG(vst_mode_ok(mode));
   VST_CHECK_ARG(dy && x && dw && workspace && N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0);
-  const int M = 4 * Cout, J = 4 * Cin, Wp = up2_wp(W), Hq = H + 1;
-  VST_CHECK_ARG(wg2_ok(0, Wp));
-  const int S = splits_for(N, M, J, Hq * Wp);
-  const int c = wsel(M);
-  const long Mpad = (M + wbm(c) - 1) / wbm(c) * wbm(c), Jpad = ((long)J + WBN - 1) / WBN * WBN;
+  const int Wp = up2_wp(W), Hq = H + 1;
+  VST_CHECK_ARG(wg2_ok(Wp));
+  WgGather g;  // the 2 x 2 edge-clamped window on the source grid, over the phase planes
+  g.Cs = Cin, g.Hs = H, g.Ws = W, g.Ho = Hq, g.Wo = Wp;
+  g.KH = g.KW = 2, g.gmode = 2, g.pad = 1;
+  const WgPlan p = wg_plan(N, 4 * Cout, g);
   float* slab = workspace;
-  float* planes = workspace + (long)N * S * Mpad * Jpad;
+  float* planes = workspace + p.floats(N);
   hipStream_t st = (hipStream_t)stream;
   const long np = (long)N * Cout * 2 * Hq * (Wp / 4);
   up2_phase_planes_kernel<<<ceil_div(np, 256), 256, 0, st>>>(dy, planes, (long)N * Cout, H, W, Wp);
   int rc = vst_launch_status();
   if (rc) return rc;
-  rc = run_wg(planes, x, slab, N, M, Cin, H, W, Hq, Wp, 2, 2, 2, 1, 1, 1, S, 0, 0, mode, st);
+  rc = run_wg(p, g, planes, x, slab, N, mode, st);
   if (rc) return rc;
   const long total = (long)Cout * 9 * Cin;
-  up2_wgrad_reduce_kernel<<<ceil_div(total, 256), 256, 0, st>>>(slab, dw, N * S, Cout, (int)Mpad, (int)Jpad, Cin,
+  up2_wgrad_reduce_kernel<<<ceil_div(total, 256), 256, 0, st>>>(slab, dw, N * p.S, Cout, p.Mpad, p.Jpad, Cin,
                                                                accumulate);
   return vst_launch_status();
 }
 
 // workspace (floats) needed by vst_conv_wgrad / vst_conv_wgrad_rowsplit / vst_gram
-long vst_wgrad_workspace(int N, int M, int J, int HWo) {
-  int c = wsel(M);
-  long Mpad = (M + wbm(c) - 1) / wbm(c) * wbm(c);
-  long Jpad = (J + WBN - 1) / WBN * WBN;
-  return (long)N * splits_for(N, M, J, HWo) * Mpad * Jpad;
-}
+long vst_wgrad_workspace(int N, int M, int J, int HWo) { return wg_plan(N, M, J, HWo).floats(N); }
 
 // the halo weight gradient (wgrad_halo.hip) applies: 3x3 stride-1 pad-1 over 32-channel blocks and
 // 16-column strips, a split-product mode, unless the call asks for the row-tiled kernel
-static bool use_wgrad_halo(int Cout, int Cin, int Hs, int Ws, int Ho, int Wo, int KH, int KW, int gmode, int stride,
-                           int pad, int up, int mode) {
-  return !(mode & VST_GEMM_PERTAP) && Ho == Hs && Wo == Ws &&
-         wgrad_halo_ok(Cout, Cin, Hs, Ws, KH, KW, stride, pad, up, gmode, mode);
+static bool use_wgrad_halo(int Cout, const WgGather& g, int mode) {
+  return !(mode & VST_GEMM_PERTAP) && g.Ho == g.Hs && g.Wo == g.Ws &&
+         wgrad_halo_ok(Cout, g.Cs, g.Hs, g.Ws, g.KH, g.KW, g.stride, g.pad, g.up, g.gmode, mode);
 }
 
 long vst_conv_wgrad_workspace(int N, int Cin, int Hs, int Ws, int Cout, int Ho, int Wo, int KH, int KW, int gmode,
@@ -1202,9 +1186,11 @@ long vst_conv_wgrad_workspace(int N, int Cin, int Hs, int Ws, int Cout, int Ho, 
   if (N <= 0 || Cin <= 0 || Cout <= 0 || Ho <= 0 || Wo <= 0 || KH <= 0 || KW <= 0 || !vst_mode_ok(mode)) return 0;
   if (vst_thin_wgrad_ok(Cout, Cin, Hs, Ws, Ho, Wo, KH, KW, gmode, stride, pad, up, mode))
     return vst_thin_wgrad_floats(N, Cout, Cin, Hs, Ws);
-  if (use_wgrad_halo(Cout, Cin, Hs, Ws, Ho, Wo, KH, KW, gmode, stride, pad, up, mode))
-    return wgrad_halo_slab_floats(N, Cin, wgrad_halo_plan(N, Cout, Cin, Hs, Ws, mode));
-  return vst_wgrad_workspace(N, Cout, KH * KW * Cin, Ho * Wo);
+  WgGather g;
+  g.Cs = Cin, g.Hs = Hs, g.Ws = Ws, g.Ho = Ho, g.Wo = Wo;
+  g.KH = KH, g.KW = KW, g.gmode = gmode, g.stride = stride, g.pad = pad, g.up = up;
+  if (use_wgrad_halo(Cout, g, mode)) return wgrad_halo_slab_floats(Cin, wgrad_halo_plan(N, Cout, Cin, Hs, Ws, mode));
+  return wg_plan(N, Cout, g).floats(N);
 }
 
 int vst_conv_wgrad(const float* dy, const float* x, float* dw, float* workspace, long ws_floats, int N, int Cin,
@@ -1213,37 +1199,34 @@ int vst_conv_wgrad(const float* dy, const float* x, float* dw, float* workspace,
   VST_CHECK_ARG(vst_mode_ok(mode));
   VST_CHECK_ARG(dy && x && dw && workspace && N > 0 && Cin > 0 && Cout > 0 && Ho > 0 && Wo > 0 && KH > 0 && KW > 0);
   VST_CHECK_ARG((gmode == 0 || gmode == 1) && (stride == 1 || stride == 2) && (up == 1 || up == 2));
+  hipStream_t st = (hipStream_t)stream;
   // at most 4 output channels: the VALU kernel (exact fp32, whatever the mode's MFMA arithmetic),
   // given the workspace vst_conv_wgrad_workspace names for it
   if (vst_thin_wgrad_ok(Cout, Cin, Hs, Ws, Ho, Wo, KH, KW, gmode, stride, pad, up, mode) &&
       ws_floats >= vst_thin_wgrad_floats(N, Cout, Cin, Hs, Ws))
-    return vst_thin_wgrad_launch(dy, x, dw, workspace, N, Cin, Hs, Ws, Cout, gmode, accumulate, (hipStream_t)stream);
-  const long rowtiled_floats = vst_wgrad_workspace(N, Cout, KH * KW * Cin, Ho * Wo);
-  bool halo = use_wgrad_halo(Cout, Cin, Hs, Ws, Ho, Wo, KH, KW, gmode, stride, pad, up, mode);
+    return vst_thin_wgrad_launch(dy, x, dw, workspace, N, Cin, Hs, Ws, Cout, gmode, accumulate, st);
+  WgGather g;
+  g.Cs = Cin, g.Hs = Hs, g.Ws = Ws, g.Ho = Ho, g.Wo = Wo;
+  g.KH = KH, g.KW = KW, g.gmode = gmode, g.stride = stride, g.pad = pad, g.up = up;
+  const WgPlan p = wg_plan(N, Cout, g);
+  bool halo = use_wgrad_halo(Cout, g, mode);
+  const WhPlan hp = halo ? wgrad_halo_plan(N, Cout, Cin, Hs, Ws, mode) : WhPlan{};
   // a workspace sized for the row-tiled kernel (the pre-halo rule) but smaller than the halo slabs
   // runs row-tiled; one smaller than both is refused
-  if (halo && ws_floats < wgrad_halo_slab_floats(N, Cin, wgrad_halo_plan(N, Cout, Cin, Hs, Ws, mode))) halo = false;
-  VST_CHECK_ARG(halo || ws_floats >= rowtiled_floats);
+  if (halo && ws_floats < wgrad_halo_slab_floats(Cin, hp)) halo = false;
+  VST_CHECK_ARG(halo || ws_floats >= p.floats(N));
+  const long total = (long)Cout * p.J;
   if (halo) {
-    const WhPlan p = wgrad_halo_plan(N, Cout, Cin, Hs, Ws, mode);
-    hipStream_t st = (hipStream_t)stream;
-    int rc = wgrad_halo_launch(p, dy, x, workspace, N, Cout, Cin, Hs, Ws, gmode, mode, st);
+    int rc = wgrad_halo_launch(hp, dy, x, workspace, N, Cout, Cin, Hs, Ws, gmode, mode, st);
     if (rc) return rc;
-    const long total = (long)Cout * 9 * Cin;
-    wgrad_reduce_kernel<<<ceil_div(total, 256), 256, 0, st>>>(workspace, dw, p.NB, Cout, p.Mpad, 9 * Cin, Cin, 3, 3, 0,
-                                                             1.0f, accumulate);
+    wgrad_reduce_kernel<<<ceil_div(total, 256), 256, 0, st>>>(workspace, dw, hp.NB, Cout, hp.Mpad, 9 * Cin, Cin, 3, 3,
+                                                             0, 1.0f, accumulate);
     return vst_launch_status();
   }
-  long J = (long)KH * KW * Cin;
-  int S = splits_for(N, Cout, J, Ho * Wo);
-  hipStream_t st = (hipStream_t)stream;
-  int rc = run_wg(dy, x, workspace, N, Cout, Cin, Hs, Ws, Ho, Wo, KH, KW, gmode, stride, pad, up, S, 0, 0, mode, st);
+  int rc = run_wg(p, g, dy, x, workspace, N, mode, st);
   if (rc) return rc;
-  int c = wsel(Cout);
-  long Mpad = (Cout + wbm(c) - 1) / wbm(c) * wbm(c), Jpad = (J + WBN - 1) / WBN * WBN;
-  long total = (long)Cout * J;
-  wgrad_reduce_kernel<<<ceil_div(total, 256), 256, 0, st>>>(workspace, dw, N * S, Cout, (int)Mpad, (int)Jpad, Cin, KH,
-                                                           KW, 0, 1.0f, accumulate);
+  wgrad_reduce_kernel<<<ceil_div(total, 256), 256, 0, st>>>(workspace, dw, N * p.S, Cout, p.Mpad, p.Jpad, Cin, KH, KW, 0,
+                                                           1.0f, accumulate);
   return vst_launch_status();
 }
 
@@ -1256,31 +1239,17 @@ int vst_conv_wgrad_rowsplit(const float* dy, const float* x, float* dw, float* w
   VST_CHECK_ARG(vst_mode_ok(mode));
   VST_CHECK_ARG(dy && x && dw && workspace && N > 0 && Cin > 0 && Cout > 0 && K > 0 && (K & 1) && K / 2 < H &&
                 K / 2 < W);
-  const int M = Cout * K, J = K * Cin, Hq = H + K - 1;
-  int S = splits_for(N, M, J, Hq * W);
+  const int Hq = H + K - 1;
+  WgGather g;  // a 1 x K reflect gather over the padded rows; A row (co, kh) reads dy row q_y - kh
+  g.Cs = Cin, g.Hs = H, g.Ws = W, g.Ho = Hq, g.Wo = W;
+  g.KW = K, g.gmode = 0, g.pad = K / 2, g.asplit = K, g.Ha = H;
+  const WgPlan p = wg_plan(N, Cout * K, g);
   hipStream_t st = (hipStream_t)stream;
-  int rc = run_wg(dy, x, workspace, N, M, Cin, H, W, Hq, W, 1, K, 0, 1, K / 2, 1, S, K, H, mode, st);
+  int rc = run_wg(p, g, dy, x, workspace, N, mode, st);
   if (rc) return rc;
-  int c = wsel(M);
-  long Mpad = (M + wbm(c) - 1) / wbm(c) * wbm(c), Jpad = ((long)J + WBN - 1) / WBN * WBN;
   long total = (long)Cout * Cin * K * K;
-  wgrad_reduce_kernel<<<ceil_div(total, 256), 256, 0, st>>>(workspace, dw, N * S, Cout, (int)Mpad, (int)Jpad, Cin, K, K,
-                                                           1, 1.0f, accumulate);
-  return vst_launch_status();
-}
-
-// G[n] = F[n] F[n]^T * scale,  F = [N][C][H*W]
-int vst_gram(const float* f, float* g, float* workspace, int N, int C, int HW, float scale, int mode, void* stream) {
-  VST_CHECK_ARG(vst_mode_ok(mode));
-  VST_CHECK_ARG(f && g && workspace && N > 0 && C > 0 && HW > 0);
-  int S = splits_for(N, C, C, HW);
-  hipStream_t st = (hipStream_t)stream;
-  int rc = run_wg(f, f, workspace, N, C, C, 1, HW, 1, HW, 1, 1, 1, 1, 0, 1, S, 0, 0, mode, st);
-  if (rc) return rc;
-  int c = wsel(C);
-  long Mpad = (C + wbm(c) - 1) / wbm(c) * wbm(c), Jpad = (C + WBN - 1) / WBN * WBN;
-  long total = (long)N * C * C;
-  gram_reduce_kernel<<<ceil_div(total, 256), 256, 0, st>>>(workspace, g, N, S, C, C, (int)Mpad, (int)Jpad, scale);
+  wgrad_reduce_kernel<<<ceil_div(total, 256), 256, 0, st>>>(workspace, dw, N * p.S, Cout, p.Mpad, p.Jpad, Cin, K, K, 1,
+                                                           1.0f, accumulate);
   return vst_launch_status();
 }
 
@@ -1290,15 +1259,20 @@ int vst_gemm_abt(const float* a, const float* b, float* out, float* workspace, i
                  int mode, void* stream) {
   VST_CHECK_ARG(vst_mode_ok(mode));
   VST_CHECK_ARG(a && b && out && workspace && N > 0 && M > 0 && J > 0 && R > 0);
-  int S = splits_for(N, M, J, R);
+  WgGather g;  // a 1x1 product over the R pixels of one row
+  g.Cs = J, g.Hs = 1, g.Ws = R, g.Ho = 1, g.Wo = R;
+  const WgPlan p = wg_plan(N, M, g);
   hipStream_t st = (hipStream_t)stream;
-  int rc = run_wg(a, b, workspace, N, M, J, 1, R, 1, R, 1, 1, 1, 1, 0, 1, S, 0, 0, mode, st);
+  int rc = run_wg(p, g, a, b, workspace, N, mode, st);
   if (rc) return rc;
-  int c = wsel(M);
-  long Mpad = (M + wbm(c) - 1) / wbm(c) * wbm(c), Jpad = ((long)J + WBN - 1) / WBN * WBN;
   long total = (long)N * M * J;
-  gram_reduce_kernel<<<ceil_div(total, 256), 256, 0, st>>>(workspace, out, N, S, M, J, (int)Mpad, (int)Jpad, scale);
+  gram_reduce_kernel<<<ceil_div(total, 256), 256, 0, st>>>(workspace, out, N, p.S, M, J, p.Mpad, p.Jpad, scale);
   return vst_launch_status();
+}
+
+// G[n] = F[n] F[n]^T * scale,  F = [N][C][H*W]
+int vst_gram(const float* f, float* g, float* workspace, int N, int C, int HW, float scale, int mode, void* stream) {
+  return vst_gemm_abt(f, f, g, workspace, N, C, C, HW, scale, mode, stream);
 }
 
 }  // extern "C"

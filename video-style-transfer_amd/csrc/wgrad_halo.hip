@@ -367,10 +367,7 @@ WhPlan wgrad_halo_plan(int N, int M, int Cs, int H, int W, int mode) {
   return p;
 }
 
-long wgrad_halo_slab_floats(int N, int Cs, const WhPlan& p) {
-  (void)N;
-  return (long)p.NB * p.Mpad * 9L * Cs;
-}
+long wgrad_halo_slab_floats(int Cs, const WhPlan& p) { return (long)p.NB * p.Mpad * 9L * Cs; }
 
 int wgrad_halo_launch(const WhPlan& p, const float* dy, const float* x, float* slab, int N, int M, int Cs, int H,
                       int W, int gmode, int mode, hipStream_t st) {
