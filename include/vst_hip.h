@@ -521,6 +521,31 @@ int vst_pfm_read_header(const char* path, int* width, int* height, int* channels
                         float* scale);
 int vst_pfm_read(const char* path, void* dst, long bytes, int offset);
 
+/* ---- AdaAttN image datasets (AA/datasets.py:16-44, 173-185; csrc/dataprep_ragged.hip) --------
+ * toTensorCrop (AA/utilities.py:31-43: Resize(size_resize), RandomCrop(size_crop), toTensor255) of N
+ * images of different source sizes in one launch, computing the crop window only:
+ *   out[i] = toTensor255(resize(src_i, (Wr_i, Hr_i), BILINEAR).crop((x0_i, y0_i, x0_i + Wc, y0_i + Hc)))
+ * as 3 x Hc x Wc fp32 at out + i * item_stride (floats), bit-exact with Pillow.
+ * The block (one buffer, int32 view `tab`, 16-byte aligned on the device):
+ *   N descriptors of VST_RAGGED_DESC_INTS int32:
+ *     [0] raster offset from the block start in 16-byte units   [1] Hs  [2] Ws  [3] x0  [4] y0
+ *     [5] tab index of the horizontal bounds, Wc x {min, count}: rows x0 .. x0 + Wc of the
+ *         vst_pil_bilinear_coeffs(Ws, Wr) bounds           [6] tab index of their taps, Wc x hks  [7] hks
+ *     [8] [9] [10] the same for the vertical axis: rows y0 .. y0 + Hc of (Hs, Hr), Hc x vks   [11] Hr  [12] Wr
+ *     [13] row0  [14] rows: the raster holds source rows row0 .. row0 + rows only, which must cover the
+ *          vertical bounds (the crop reads no other row, so the others need not be copied)
+ *   then the tables, then the rasters (rows x Ws x 3 uint8, PIL's interleaved RGB), each followed by at
+ *   least 3 bytes that belong to the block (the kernel loads aligned dwords).
+ * block_host is the host copy the device block was filled from: every descriptor, offset and bound is
+ * validated on it before the launch (vst_pil_ragged_check alone needs no GPU).
+ * vst_pil_ragged_tile_paths: per item, how many 64 x 8 output tiles take the LDS-tiled path and how many
+ * the per-pixel path (source window of a tile beyond the LDS bounds). */
+#define VST_RAGGED_DESC_INTS 16
+int vst_pil_ragged_check(const void* block_host, long block_bytes, int N, int Hc, int Wc);
+int vst_pil_resize_crop_ragged(const void* block_dev, const void* block_host, long block_bytes, int N, int Hc, int Wc,
+                               float* out, long item_stride, void* stream);
+int vst_pil_ragged_tile_paths(const void* block_host, long block_bytes, int N, int Hc, int Wc, int* tiled, int* fallback);
+
 /* ---- evaluation metrics (csrc/metrics.hip) --------------------------------------------------
  * Fused masked warping error of B frame pairs (RT/utilities.py:231-236 temporal_errors_sintel: mask *
  * MSELoss(none)(styled0, warp(styled1, flow)), .mean(); AA/exps_sintel.py:79-100: clamp(0,255)/255 of

@@ -174,9 +174,14 @@ class AdaAttNTrainer:
     def step_batch(self, batch):
         """One step on a loader batch (content1, content2, style) (AA/train_video.py:78-81): the three
         encodings as one VGG19 pass of 3B (a [3, B, 3, H, W] buffer); an already stacked buffer is
-        used as is."""
+        used as is.  An image batch (AA/train_image.py:69-74) -- a (content, style) pair or a
+        [2, B, 3, H, W] buffer, CocoWikiArtLoader's -- takes `image_step`."""
         if isinstance(batch, torch.Tensor):
+            if batch.shape[0] == 2:
+                return self.image_step(batch[0], batch[1])
             return self.step(batch)
+        if len(batch) == 2:
+            return self.image_step(*batch)
         c1, c2, s = batch
         return self.step(torch.stack([c1, c2, s]))
 

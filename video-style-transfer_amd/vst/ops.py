@@ -1890,6 +1890,120 @@ def pil_resize_to_tensor255(images, size, out=None):
     return _pil_resize(images, size, out, 0)
 
 
+# ---------------------------------------------------- AdaAttN image datasets: ragged resize-and-crop
+RAGGED_DESC_INTS = 16  # VST_RAGGED_DESC_INTS (include/vst_hip.h)
+_PIL_HOST_TABLES = {}
+
+
+def _pil_host_tables(in_size, out_size):
+    t = _PIL_HOST_TABLES.get((in_size, out_size))
+    if t is None:
+        t = _PIL_HOST_TABLES[(in_size, out_size)] = pil_bilinear_coeffs(in_size, out_size)
+    return t
+
+
+class RaggedStaged:
+    """One host block of a ragged resize-and-crop batch (layout: include/vst_hip.h)."""
+
+    def __init__(self, host, n, crop):
+        self.host, self.n, self.crop = host, n, crop
+
+    @property
+    def desc(self):
+        """(n, RAGGED_DESC_INTS) int32 view of the descriptors."""
+        return self.host.numpy()[:self.n * RAGGED_DESC_INTS * 4].view(np.int32).reshape(self.n, RAGGED_DESC_INTS)
+
+    @property
+    def ints(self):
+        """int32 view of the whole block (descriptor table indices point into it)."""
+        return self.host.numpy()[:self.host.numel() // 4 * 4].view(np.int32)
+
+    def tile_paths(self):
+        """Per item (tiles on the LDS-tiled path, tiles on the per-pixel path)."""
+        tiled, fallback = np.zeros(self.n, np.int32), np.zeros(self.n, np.int32)
+        ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))  # noqa: E731
+        lib.vst_pil_ragged_tile_paths(self.host.data_ptr(), self.host.numel(), self.n, self.crop[0], self.crop[1],
+                                      ip(tiled), ip(fallback))
+        return tiled, fallback
+
+
+def stage_ragged(images, resize, crop, origins):
+    """Host half of the ragged resize-and-crop: images = decoded (Hs, Ws, 3) uint8 rasters of any sizes,
+    resize = (Hr, Wr) for all items or one per item, crop = (Hc, Wc) for the batch, origins = (y0, x0)
+    per item.  Builds ONE (pinned, when a GPU is present) uint8 block: descriptors, the Pillow tables
+    of every item sliced to its crop rows / columns, then the rasters at 16-byte offsets -- of each
+    raster only the source rows its crop reads."""
+    n = len(images)
+    Hc, Wc = (int(v) for v in crop)
+    if len(origins) != n:
+        raise VstError(f"stage_ragged: {n} images, {len(origins)} origins")
+    sizes = [tuple(resize)] * n if n == 0 or np.isscalar(resize[0]) else [tuple(r) for r in resize]
+    if len(sizes) != n:
+        raise VstError(f"stage_ragged: {n} images, {len(sizes)} resize targets")
+    D = RAGGED_DESC_INTS
+    items, at = [], n * D  # `at`: running int32 index behind the descriptors
+    for a, (Hr, Wr), (y0, x0) in zip(images, sizes, origins):
+        if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
+            raise VstError(f"stage_ragged: need (H, W, 3) uint8 rasters, got {a.dtype} {a.shape}")
+        if not (0 <= y0 <= Hr - Hc and 0 <= x0 <= Wr - Wc):
+            raise VstError(f"stage_ragged: crop {Hc}x{Wc} at ({y0}, {x0}) leaves the {Hr}x{Wr} image")
+        Hs, Ws = a.shape[:2]
+        hb, hk = _pil_host_tables(Ws, Wr)
+        vb, vk = _pil_host_tables(Hs, Hr)
+        tabs = (hb[x0:x0 + Wc], hk[x0:x0 + Wc], vb[y0:y0 + Hc], vk[y0:y0 + Hc])
+        row0, row1 = int(tabs[2][0, 0]), int(tabs[2][-1].sum())  # the source rows the crop reads
+        a = a[row0:row1]
+        idx = []
+        for t in tabs:
+            idx.append(at)
+            at += t.size
+        items.append((a, (Hs, Ws, x0, y0, Hr, Wr, row0, row1 - row0), tabs, idx))
+    at_bytes = -(-at * 4 // 16) * 16
+    offs = []
+    for a, *_ in items:
+        offs.append(at_bytes)
+        at_bytes += -(-a.size // 16) * 16
+    total = at_bytes + 16
+    host = torch.empty(total, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    raw = host.numpy()
+    ints = raw[:total // 4 * 4].view(np.int32)
+    raw[at * 4:offs[0] if offs else total] = 0  # the gaps are never used; zeroed so equal batches are equal blocks
+    for (a, *_), off in zip(items, offs):
+        raw[off + a.size:off + -(-a.size // 16) * 16] = 0
+    raw[total - 16:] = 0
+    for i, ((a, (Hs, Ws, x0, y0, Hr, Wr, row0, rows), tabs, idx), off) in enumerate(zip(items, offs)):
+        ints[i * D:(i + 1) * D] = (off // 16, Hs, Ws, x0, y0, idx[0], idx[1], tabs[1].shape[1], idx[2], idx[3],
+                                   tabs[3].shape[1], Hr, Wr, row0, rows, 0)
+        for t, j in zip(tabs, idx):
+            ints[j:j + t.size] = t.reshape(-1)
+        raw[off:off + a.size] = a.reshape(-1)
+    return RaggedStaged(host, n, (Hc, Wc))
+
+
+def resize_crop_ragged(staged, out=None, device=None, block=None):
+    """Device half: ONE non_blocking copy of the staged block and ONE launch (vst_pil_resize_crop_ragged):
+    out[i] = toTensor255(resize(image_i, BILINEAR).crop(window_i)), (n, 3, Hc, Wc) fp32, bit-exact with
+    Pillow.  `out` may be a slice of a larger buffer (items at a uniform stride, each contiguous).
+    block: a device copy of staged.host made earlier (tools/aa_dataprep_bench.py times the launch alone)."""
+    n, (Hc, Wc) = staged.n, staged.crop
+    if out is None:
+        dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty((n, 3, Hc, Wc), dtype=torch.float32, device=dev)
+    if tuple(out.shape) != (n, 3, Hc, Wc):
+        raise VstError(f"ragged crop: out shape {tuple(out.shape)} != {(n, 3, Hc, Wc)}")
+    if n == 0:
+        return out
+    base, item_stride = ptr_rows(out)
+    if block is None:
+        block = torch.empty(staged.host.numel(), dtype=torch.uint8, device=out.device)
+        block.copy_(staged.host, non_blocking=True)
+    elif block.numel() != staged.host.numel() or block.device != out.device or block.dtype != torch.uint8:
+        raise VstError("ragged crop: block is not a device copy of the staged block")
+    lib.vst_pil_resize_crop_ragged(block.data_ptr(), staged.host.data_ptr(), staged.host.numel(), n, Hc, Wc, base,
+                                   item_stride if n > 1 else 3 * Hc * Wc, stream())
+    return out
+
+
 def apply_motion_mask(mask, motion):
     """mask *= 1 - (toTensor(motion.resize(size, BILINEAR)) != 0) (RC/datasets.py:138-144), in place:
     mask (N, H, W) fp32 0/1, motion (N, Hs, Ws) uint8 boundary images."""
