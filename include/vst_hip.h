@@ -145,6 +145,16 @@ int vst_conv_dgrad_thin(const float* dy, const float* w, const float* mask, floa
  * the image alone. */
 int vst_conv_thin_fwd(const float* x, const float* w, const float* bias, float* out, void* frames, int N, int Cin,
                       int H, int W, int Cout, int reflect, int swap_rb, void* stream);
+/* The RTNSTV stem at inference (RT/network.py:71 conv1 behind RT/utilities.py:182-191): the 3x3 stride-1
+ * reflect-pad-1 conv of a 3-channel image read straight from cv2 frames ([N][H][W][3] uint8; bgr: BGR
+ * byte order, converted to RGB), out ([N][Cout][H][W] fp32) = b[co] + sum W[co][ci][kh][kw] *
+ * Xpad[ci][y + kh][x + kw] with X the byte as vst_frames_to_tensor gives it ((v / 255) * 255), in exact
+ * fp32 on the VALU (no MFMA, no GEMM mode); the fp32 planes of the frame are never written.  One fixed FMA
+ * order (from 0 over ci, kh, kw ascending, then + b; csrc/stem.hip): a frame in a batch is bitwise the
+ * frame alone.  w: [Cout][3][3][3]; bias may be NULL; Cout in {4, 8, 12, 16}, H >= 2, W % 4 == 0, N <= 65535;
+ * frames 4-byte, out 16-byte aligned. */
+int vst_conv_stem_u8(const void* frames, const float* w, const float* bias, float* out, int N, int H, int W,
+                     int Cout, int bgr, void* stream);
 /* Thin-channel convolutions (RC/network.py:155 conv1 = ConvLayer(3, 48, 9), :169 deconv3 =
  * ConvTanh(48, 3, 9) backward, VGG conv1_1): a tensor with C*K <= Cu channels is kw-unfolded,
  *   out[n][c*K + kw][y][v] = src[n][c][y][v + sgn*kw + off]  (reflect or zero outside; zero channels
@@ -275,6 +285,27 @@ int vst_instnorm_fwd(const float* x, const float* w, const float* b, const float
 int vst_instnorm_bwd(const float* gy, const float* x, const float* y, const float* b, const float* stats,
                      const float* w, float* gx, float* gw, float* gb, float* gbias_prev, float* partial, int N, int C,
                      int HW, int relu, int accumulate, void* stream);
+/* Split-plane forward, for launches of few planes (inference at one frame per forward: 16 planes of
+ * 230 400 elements, or 3), where vst_instnorm_fwd's one workgroup per plane leaves the chip idle.  A plane
+ * is cut into S contiguous chunks (1 <= S <= VST_INSTNORM_MAX_CHUNKS; chunk k holds elements
+ * [HW * k / S, HW * (k + 1) / S), counted in groups of 4 when HW % 4 == 0) and every grid is
+ * (plane, chunk).  Forward only.  partial: planes * S * 2 doubles of the caller's.
+ *   vst_instnorm_moments: partial[(plane * S + k) * 2] = {sum, sum of squares} of chunk k (fp64, no atomics);
+ *   vst_instnorm_apply:   every block adds its plane's S partials in chunk order (fp64), forms mean and rstd
+ *     exactly as vst_instnorm_fwd (biased variance, eps inside the root, rounded to fp32 last) and writes
+ *     y = [relu]((x - mean) * rstd * w + b) [+ res] over its chunk with the same element arithmetic, so for
+ *     equal mean and rstd an element is bitwise vst_instnorm_fwd's; chunk 0 writes stats [N*C][2];
+ *   vst_instnorm_tanh_frames (C == 3: the RTNSTV tail, RT/network.py:24-25, 93 and RT/utilities.py:328-330):
+ *     the same reduction and affine, then (tanh(.) + 1) / 2 * 255 with vst_tanh_image_fwd's arithmetic and
+ *     the clamp / truncation of vst_tensor_to_frames into frames ([N][H*W][3] uint8; bgr: BGR order), the
+ *     three channels of a pixel by one thread; the fp32 image is never written.
+ * S is the caller's choice; a frame's statistics do not depend on the batch it is in for a fixed S. */
+#define VST_INSTNORM_MAX_CHUNKS 256
+int vst_instnorm_moments(const float* x, double* partial, int planes, int HW, int S, void* stream);
+int vst_instnorm_apply(const float* x, const double* partial, const float* w, const float* b, const float* res,
+                       float* y, float* stats, int N, int C, int HW, int S, float eps, int relu, void* stream);
+int vst_instnorm_tanh_frames(const float* x, const double* partial, const float* w, const float* b, void* frames,
+                             int N, int HW, int S, float eps, int bgr, void* stream);
 /* out[c] (+)= sum_{n,i} x[n][c][i]; partial: N*C floats (conv bias gradient) */
 int vst_channel_sum(const float* x, float* out, float* partial, int N, int C, int HW, int accumulate, void* stream);
 

@@ -9,6 +9,7 @@
 //     consecutive content/stylised frame pairs, written to a device slot (no host sync per frame).
 // All three are HBM-bound streams: 4 pixels per thread, dwordx4 fp32 accesses per plane and
 // three dword accesses for the 12 interleaved bytes.
+#include "frame_elem.h"
 #include "vst_common.h"
 #include "vst_hip.h"
 
@@ -17,14 +18,8 @@ namespace {
 constexpr int FT = 256;
 constexpr int MAXB = 2048;
 
-__device__ __forceinline__ float to255(uint32_t b) { return ((float)b / 255.0f) * 255.0f; }
-
-__device__ __forceinline__ uint32_t to_u8(float v) {
-  // clamp(0, 255) then numpy float32 -> uint8 (C truncation); NaN stays NaN in the fp32 copy
-  return (uint32_t)(int)v;
-}
-
-__device__ __forceinline__ float clamp255(float v) { return v < 0.f ? 0.f : (v > 255.f ? 255.f : v); }
+// to255, clamp255 and to_u8 come from frame_elem.h: ToTensor * 255; clamp(0, 255) then numpy
+// float32 -> uint8 (C truncation); NaN stays NaN in the fp32 copy
 
 // one thread = 4 consecutive pixels of one frame; HW % 4 == 0
 __global__ void frames_to_tensor_v4(const uint32_t* __restrict__ src, float* __restrict__ out, long groups,

@@ -10,6 +10,7 @@
 // Reference semantics: RC/train_single/train_candy.py:90-145 (FTL, OTL, content, style, TV),
 // RC/utilities.py:101-106 (vgg_normalize), RC/network.py:83-85 (ConvTanh),
 // torch.optim.Adam defaults (train_candy.py:44,152).
+#include "frame_elem.h"
 #include "vst_common.h"
 #include "vst_hip.h"
 
@@ -457,7 +458,7 @@ __global__ void tanh_image_kernel(const float* __restrict__ v, float* __restrict
   if (i >= n) return;
   float th = tanhf(v[i]);
   t[i] = th;
-  y[i] = image ? ((th + 1.0f) / 2.0f) * 255.0f : th;
+  y[i] = image ? tanh_to_image(th) : th;
 }
 
 __global__ void tanh_image_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ t, float* __restrict__ gv,

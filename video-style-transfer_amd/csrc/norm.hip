@@ -3,6 +3,7 @@
 // One workgroup per (n, c) plane; fp64 accumulation of the per-plane moments, plain (non-atomic)
 // per-plane partials for the affine/bias gradients summed over n by a second tiny kernel
 // (deterministic).
+#include "frame_elem.h"
 #include "vst_common.h"
 #include "vst_hip.h"
 
@@ -441,6 +442,212 @@ __global__ __launch_bounds__(LDS_NT) void in_bwd_lds_kernel(const float* __restr
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Split-plane forward (inference): the kernels above give a plane to ONE workgroup, which at one frame
+// per forward leaves most of the chip idle (16 planes of 230 400 elements, or 3).  Here a plane is cut
+// into S contiguous chunks (bounds a multiple of 4 elements when HW % 4 == 0) and the grid is
+// (plane, chunk): in_moments_kernel writes each chunk's {sum, sum of squares} (fp64, no atomics),
+// in_apply_kernel / in_tanh_frames_kernel sum a plane's S partials in chunk order, form mean and rstd
+// exactly as in_fwd_kernel does and write their own chunk.  For equal mean and rstd an element is
+// bitwise what in_fwd_kernel writes (the same in_affine).
+constexpr int SP_NT = 256;
+static_assert(VST_INSTNORM_MAX_CHUNKS <= SP_NT, "one thread stages one chunk's partial");
+
+// elements [lo, hi) of chunk k of S
+__device__ __forceinline__ void chunk_bounds(int HW, int S, int k, int& lo, int& hi) {
+  if ((HW & 3) == 0) {
+    const long n4 = HW >> 2;
+    lo = (int)(n4 * k / S) * 4;
+    hi = (int)(n4 * (k + 1) / S) * 4;
+  } else {
+    lo = (int)((long)HW * k / S);
+    hi = (int)((long)HW * (k + 1) / S);
+  }
+}
+
+// vec: HW % 4 == 0 and x 16-byte aligned (the chunk bounds do not depend on the alignment)
+__global__ __launch_bounds__(SP_NT) void in_moments_kernel(const float* __restrict__ x, double* __restrict__ partial,
+                                                           int HW, int S, int vec) {
+  __shared__ double sh[2][SP_NT / 64];
+  const long plane = blockIdx.x / S;
+  const int k = (int)(blockIdx.x - plane * S);
+  int lo, hi;
+  chunk_bounds(HW, S, k, lo, hi);
+  const float* xp = x + plane * HW;
+  double s1 = 0.0, s2 = 0.0;
+  if (vec) {
+    const float4* x4 = reinterpret_cast<const float4*>(xp);
+    auto acc = [&](const float4& v) {
+      s1 += ((double)v.x + v.y) + ((double)v.z + v.w);
+      s2 += ((double)v.x * v.x + (double)v.y * v.y) + ((double)v.z * v.z + (double)v.w * v.w);
+    };
+    const int e4 = hi >> 2;
+    int i = (lo >> 2) + threadIdx.x;
+    for (; i + SP_NT < e4; i += 2 * SP_NT) {
+      const float4 v = x4[i], u = x4[i + SP_NT];
+      acc(v);
+      acc(u);
+    }
+    if (i < e4) acc(x4[i]);
+  } else {
+    for (int i = lo + threadIdx.x; i < hi; i += SP_NT) {
+      double v = xp[i];
+      s1 += v;
+      s2 += v * v;
+    }
+  }
+  s1 = block_sum<double, SP_NT>(s1, sh[0]);
+  s2 = block_sum<double, SP_NT>(s2, sh[1]);
+  if (threadIdx.x == 0) {
+    partial[2 * (long)blockIdx.x] = s1;
+    partial[2 * (long)blockIdx.x + 1] = s2;
+  }
+}
+
+// A plane's S chunk partials -> LDS (one per thread), then every thread adds them in chunk order and
+// forms mean / rstd as in_fwd_kernel: biased variance, eps inside the root, rounded to fp32 last.
+// sp: VST_INSTNORM_MAX_CHUNKS entries.  Ends with the block past its barrier.
+__device__ __forceinline__ void plane_stats(const double* __restrict__ pp, double2* sp, int S, int HW, float eps,
+                                            float& mean, float& rstd) {
+  if ((int)threadIdx.x < S) sp[threadIdx.x] = make_double2(pp[2 * threadIdx.x], pp[2 * threadIdx.x + 1]);
+  __syncthreads();
+  double s1 = 0.0, s2 = 0.0;
+  for (int k = 0; k < S; ++k) {
+    const double2 p = sp[k];
+    s1 += p.x;
+    s2 += p.y;
+  }
+  const double mean_d = s1 / HW;
+  double var_d = s2 / HW - mean_d * mean_d;
+  var_d = var_d < 0.0 ? 0.0 : var_d;
+  mean = (float)mean_d;
+  rstd = (float)(1.0 / sqrt(var_d + (double)eps));
+}
+
+// y = [relu]( (x - mean) * rstd * w + b ) [+ res] over chunk k of a plane; vec: HW % 4 == 0 and x, res, y
+// 16-byte aligned
+__global__ __launch_bounds__(SP_NT) void in_apply_kernel(const float* __restrict__ x, const double* __restrict__ partial,
+                                                         const float* __restrict__ w, const float* __restrict__ b,
+                                                         const float* __restrict__ res, float* __restrict__ y,
+                                                         float* __restrict__ stats, int C, int HW, int S, float eps,
+                                                         int relu, int vec) {
+  __shared__ double2 sp[VST_INSTNORM_MAX_CHUNKS];
+  const long plane = blockIdx.x / S;
+  const int k = (int)(blockIdx.x - plane * S);
+  const int c = (int)(plane % C);
+  float mean, rstd;
+  plane_stats(partial + 2 * plane * S, sp, S, HW, eps, mean, rstd);
+  if (k == 0 && threadIdx.x == 0) {
+    stats[2 * plane] = mean;
+    stats[2 * plane + 1] = rstd;
+  }
+  int lo, hi;
+  chunk_bounds(HW, S, k, lo, hi);
+  const float wc = w[c], bc = b[c];
+  const float* xp = x + plane * HW;
+  float* yp = y + plane * HW;
+  const float* rp = res ? res + plane * HW : nullptr;
+  if (vec) {
+    const float4* x4 = reinterpret_cast<const float4*>(xp);
+    const float4* r4 = reinterpret_cast<const float4*>(rp);
+    float4* y4 = reinterpret_cast<float4*>(yp);
+    auto out = [&](const float4& v, int i) {
+      float o[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        o[j] = in_affine(o[j], mean, rstd, wc, bc);
+        if (relu) o[j] = fmaxf(o[j], 0.f);
+      }
+      if (rp) {
+        const float4 r = r4[i];
+        o[0] += r.x;
+        o[1] += r.y;
+        o[2] += r.z;
+        o[3] += r.w;
+      }
+      y4[i] = make_float4(o[0], o[1], o[2], o[3]);
+    };
+    const int e4 = hi >> 2;
+    int i = (lo >> 2) + threadIdx.x;
+    for (; i + SP_NT < e4; i += 2 * SP_NT) {
+      const float4 v = x4[i], u = x4[i + SP_NT];
+      out(v, i);
+      out(u, i + SP_NT);
+    }
+    if (i < e4) out(x4[i], i);
+  } else {
+    for (int i = lo + threadIdx.x; i < hi; i += SP_NT) {
+      float o = in_affine(xp[i], mean, rstd, wc, bc);
+      if (relu) o = fmaxf(o, 0.f);
+      if (rp) o += rp[i];
+      yp[i] = o;
+    }
+  }
+}
+
+// The RTNSTV tail (RT/network.py:24-25, 93; RT/utilities.py:328-330) on x = conv4's output, C = 3:
+// InstanceNorm, Tanh, (t + 1) / 2 * 255, clamp(0, 255), HWC, RGB2BGR (swap), astype(uint8), in one
+// pass: frames[n][p][:] = to_u8(clamp255(tanh_to_image(tanhf(in_affine(x[n][c][p], ...))))).  A thread
+// makes the three channels of its pixels (four at a time when vec: HW % 4 == 0, x 16-byte and frames
+// 4-byte aligned); the fp32 image is never written.
+__global__ __launch_bounds__(SP_NT) void in_tanh_frames_kernel(const float* __restrict__ x,
+                                                               const double* __restrict__ partial,
+                                                               const float* __restrict__ w, const float* __restrict__ b,
+                                                               uint8_t* __restrict__ frames, int HW, int S, float eps,
+                                                               int swap, int vec) {
+  __shared__ double2 sp[VST_INSTNORM_MAX_CHUNKS];
+  const long n = blockIdx.x / S;
+  const int k = (int)(blockIdx.x - n * S);
+  float mean[3], rstd[3], wc[3], bc[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    plane_stats(partial + 2 * (n * 3 + c) * S, sp, S, HW, eps, mean[c], rstd[c]);
+    __syncthreads();  // sp is staged again for the next channel
+    wc[c] = w[c];
+    bc[c] = b[c];
+  }
+  auto px = [&](float v, int c) -> uint32_t {
+    return to_u8(clamp255(tanh_to_image(tanhf(in_affine(v, mean[c], rstd[c], wc[c], bc[c])))));
+  };
+  int lo, hi;
+  chunk_bounds(HW, S, k, lo, hi);
+  const float* xp = x + n * 3 * HW;
+  if (vec) {
+    const float4* x4 = reinterpret_cast<const float4*>(xp);
+    uint32_t* d32 = reinterpret_cast<uint32_t*>(frames) + n * 3 * (HW >> 2);
+    const int HW4 = HW >> 2, e4 = hi >> 2;
+    for (int i = (lo >> 2) + threadIdx.x; i < e4; i += SP_NT) {
+      uint32_t q[12];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float4 v = x4[(long)c * HW4 + i];
+        q[c] = px(v.x, c);
+        q[3 + c] = px(v.y, c);
+        q[6 + c] = px(v.z, c);
+        q[9 + c] = px(v.w, c);
+      }
+      if (swap) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const uint32_t t0 = q[3 * j];
+          q[3 * j] = q[3 * j + 2];
+          q[3 * j + 2] = t0;
+        }
+      }
+      uint32_t* d = d32 + 3 * (long)i;
+      d[0] = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
+      d[1] = q[4] | (q[5] << 8) | (q[6] << 16) | (q[7] << 24);
+      d[2] = q[8] | (q[9] << 8) | (q[10] << 16) | (q[11] << 24);
+    }
+  } else {
+    uint8_t* d = frames + n * 3 * HW;
+    for (int i = lo + threadIdx.x; i < hi; i += SP_NT) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) d[3 * (long)i + (swap ? 2 - c : c)] = (uint8_t)px(xp[(long)c * HW + i], c);
+    }
+  }
+}
+
 // dst_k[c] (+)= sum_n partial[(n*C + c)*NP + k] for the non-null dst_k
 __global__ void sum_over_n_kernel(const float* __restrict__ partial, int N, int C, int NP, float* d0, float* d1,
                                   float* d2, int accumulate) {
@@ -501,6 +708,38 @@ int vst_instnorm_fwd(const float* x, const float* w, const float* b, const float
     in_fwd_reg_kernel<1024, 8><<<N * C, 1024, 0, st>>>(x, w, b, res, y, stats, C, HW, eps, relu);
   else
     in_fwd_kernel<IN_BIG_NT><<<N * C, IN_BIG_NT, 0, st>>>(x, w, b, res, y, stats, C, HW, eps, relu);
+  return vst_launch_status();
+}
+
+// Split-plane forward: the three entries below share `partial`, planes * S * 2 doubles of the caller's
+// ({sum, sum of squares} of chunk k of plane p at (p * S + k) * 2).
+static bool split_args_ok(long planes, int HW, int S) {
+  return planes > 0 && HW > 0 && S >= 1 && S <= VST_INSTNORM_MAX_CHUNKS && planes * S <= 0x7fffffffL;
+}
+static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+int vst_instnorm_moments(const float* x, double* partial, int planes, int HW, int S, void* stream) {
+  VST_CHECK_ARG(x && partial && split_args_ok(planes, HW, S) && ((uintptr_t)partial & 7) == 0);
+  const int vec = (HW & 3) == 0 && al16(x);
+  in_moments_kernel<<<planes * S, SP_NT, 0, (hipStream_t)stream>>>(x, partial, HW, S, vec);
+  return vst_launch_status();
+}
+
+int vst_instnorm_apply(const float* x, const double* partial, const float* w, const float* b, const float* res,
+                       float* y, float* stats, int N, int C, int HW, int S, float eps, int relu, void* stream) {
+  VST_CHECK_ARG(x && partial && w && b && y && stats && N > 0 && C > 0 && split_args_ok((long)N * C, HW, S));
+  const int vec = (HW & 3) == 0 && al16(x) && al16(y) && al16(res);
+  in_apply_kernel<<<N * C * S, SP_NT, 0, (hipStream_t)stream>>>(x, partial, w, b, res, y, stats, C, HW, S, eps, relu,
+                                                                 vec);
+  return vst_launch_status();
+}
+
+int vst_instnorm_tanh_frames(const float* x, const double* partial, const float* w, const float* b, void* frames,
+                             int N, int HW, int S, float eps, int bgr, void* stream) {
+  VST_CHECK_ARG(x && partial && w && b && frames && N > 0 && split_args_ok((long)N * 3, HW, S));
+  const int vec = (HW & 3) == 0 && al16(x) && ((uintptr_t)frames & 3) == 0;
+  in_tanh_frames_kernel<<<N * S, SP_NT, 0, (hipStream_t)stream>>>(x, partial, w, b, (uint8_t*)frames, HW, S, eps, bgr,
+                                                                   vec);
   return vst_launch_status();
 }
 

@@ -6,5 +6,5 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from vst.rtnstv.utilities import *  # noqa: E402,F401,F403
-from vst.rtnstv.utilities import (flow_warp_mask, gram_matrix, list_files, read_sintel_flow,  # noqa: E402,F401
-                                   temporal_errors_sintel, vgg_normalize, warp)
+from vst.rtnstv.utilities import (Inference, cvframe_to_tensor, flow_warp_mask, gram_matrix,  # noqa: E402,F401
+                                   list_files, read_sintel_flow, temporal_errors_sintel, vgg_normalize, warp)

@@ -1798,6 +1798,141 @@ def tanh_image(v, image=True):
     return TanhImageFn.apply(v, image)
 
 
+# ---------------------------------------------------------------- RTNSTV inference (RT/utilities.py:296-332)
+# Forward-only ops of vst.rtnstv.inference: plain functions, no autograd Function.
+IN_SPLIT = os.environ.get("VST_IN_SPLIT", "1") != "0"  # A/B: 0 = the one-workgroup-per-plane kernel everywhere
+IN_MAX_CHUNKS = 256  # VST_INSTNORM_MAX_CHUNKS (include/vst_hip.h)
+# Chunks per plane of the split-plane InstanceNorm forward, from (C, HW) alone -- never from N, so a
+# frame's statistics do not depend on the batch it is in.  Set from the measured table of
+# tools/rt_infer_bench.py (profiles/rt_infer_bench.json): planes above IN_SPLIT_MIN_HW
+# elements are cut until a frame's C planes make IN_SPLIT_BLOCKS workgroups, a chunk keeping at least
+# IN_SPLIT_MIN_CHUNK elements (14 float4 per thread) -- S = 32 for 16 x 230 400, 16 for 32 x 57 600, 64 for
+# 3 x 230 400, the fastest or within 0.5 us of it in each sweep; smaller planes (48 x 14 400) stay on
+# vst_instnorm_fwd's register-resident one-read kernels, which won there (S = 1).
+IN_SPLIT_MIN_HW = 32768
+IN_SPLIT_BLOCKS = 512
+IN_SPLIT_MIN_CHUNK = 3584
+
+
+def instnorm_chunks(C, HW):
+    """The host rule for S (see above); 1 means vst_instnorm_fwd."""
+    if not IN_SPLIT or HW <= IN_SPLIT_MIN_HW:
+        return 1
+    s = min(-(-IN_SPLIT_BLOCKS // C), HW // IN_SPLIT_MIN_CHUNK, IN_MAX_CHUNKS)
+    return max(1, s)
+
+
+def _chunks(C, HW, chunks):
+    if not IN_SPLIT:
+        return 1
+    if chunks is None:
+        return instnorm_chunks(C, HW)
+    s = int(chunks)
+    if not 1 <= s <= IN_MAX_CHUNKS:
+        raise VstError(f"chunks must be in 1..{IN_MAX_CHUNKS}, got {chunks}")
+    return s
+
+
+def _affine(w, b, C, name):
+    w, b = w.detach().contiguous(), b.detach().contiguous()
+    if tuple(w.shape) != (C,) or tuple(b.shape) != (C,):
+        raise VstError(f"{name}: weight {tuple(w.shape)} / bias {tuple(b.shape)} do not match {C} channels")
+    return w, b
+
+
+def _moments(x, planes, HW, S):
+    part = torch.empty((planes * S * 2,), dtype=torch.float64, device=x.device)
+    lib.vst_instnorm_moments(ptr(x), part.data_ptr(), planes, HW, S, stream())
+    return part
+
+
+def instance_norm_infer(x, w, b, relu=False, res=None, eps=1e-5, chunks=None):
+    """InstanceNorm2d(affine) [-> ReLU] [+ res] at inference: ops.instance_norm's result without an
+    autograd graph, on the split-plane kernels (vst_instnorm_moments + vst_instnorm_apply) when the rule
+    -- or `chunks`, for tests and A/B runs -- cuts a plane into S > 1 chunks, else on vst_instnorm_fwd
+    (bitwise ops.instance_norm).  VST_IN_SPLIT=0 forces S = 1."""
+    x = _check(x, "instance_norm input", 4).detach()
+    N, C, H, W = x.shape
+    HW = H * W
+    w, b = _affine(w, b, C, "instance_norm_infer")
+    S = _chunks(C, HW, chunks)
+    res_c = None
+    if res is not None:
+        res_c = _check(res, "instance_norm residual", 4).detach()
+        if res_c.shape != x.shape:
+            raise VstError(f"instance_norm_infer: residual {tuple(res_c.shape)} != input {tuple(x.shape)}")
+    y = _empty(x.shape, x)
+    stats = _empty((N * C * 2,), x)
+    if S == 1:
+        lib.vst_instnorm_fwd(ptr(x), ptr(w), ptr(b), ptr(res_c), ptr(y), ptr(stats), N, C, HW, float(eps), int(relu),
+                             stream())
+    else:
+        part = _moments(x, N * C, HW, S)
+        lib.vst_instnorm_apply(ptr(x), part.data_ptr(), ptr(w), ptr(b), ptr(res_c), ptr(y), ptr(stats), N, C, HW, S,
+                               float(eps), int(relu), stream())
+    return y
+
+
+def instance_norm_tanh_frames(x, w, b, eps=1e-5, bgr=True, frames=None, chunks=None):
+    """The RTNSTV tail on conv4's output x (N,3,H,W): InstanceNorm -> Tanh -> (t + 1) / 2 * 255 ->
+    clamp(0, 255) -> HWC [-> BGR] -> truncating uint8 in one pass (vst_instnorm_tanh_frames), byte for
+    byte tensor_to_frames(tanh_image(instance_norm_infer(x, w, b, chunks=chunks))).  Returns (N,H,W,3)
+    uint8; the fp32 image is never written.  Where S = 1 (the rule's choice for small planes, chunks=1, or
+    VST_IN_SPLIT=0) that three-kernel chain runs instead, on vst_instnorm_fwd."""
+    x = _check(x, "instance_norm input", 4).detach()
+    N, C, H, W = x.shape
+    if C != 3:
+        raise VstError(f"instance_norm_tanh_frames: stylised frames have 3 channels, got {C}")
+    w, b = _affine(w, b, 3, "instance_norm_tanh_frames")
+    if frames is None:
+        frames = torch.empty((N, H, W, 3), dtype=torch.uint8, device=x.device)
+    elif tuple(frames.shape) != (N, H, W, 3):
+        raise VstError(f"instance_norm_tanh_frames: frames shape {tuple(frames.shape)} != {(N, H, W, 3)}")
+    S = _chunks(3, H * W, chunks)
+    if S == 1:  # the rule keeps this plane size on vst_instnorm_fwd: the three kernels it feeds
+        with torch.no_grad():
+            return tensor_to_frames(tanh_image(instance_norm_infer(x, w, b, eps=eps, chunks=1), image=True), bgr=bgr,
+                                    frames=frames)
+    part = _moments(x, N * 3, H * W, S)
+    lib.vst_instnorm_tanh_frames(ptr(x), part.data_ptr(), ptr(w), ptr(b), _ptr_u8(frames, "frames"), N, H * W, S,
+                                 float(eps), int(bool(bgr)), stream())
+    return frames
+
+
+def conv_stem_u8_ok(Cout, H, W, N=1):
+    return Cout % 4 == 0 and 4 <= Cout <= 16 and W % 4 == 0 and W >= 4 and H >= 2 and N <= 65535
+
+
+def conv_stem_u8(frames, w, b=None, bgr=True, out=None):
+    """RT/utilities.py:182-191 cvframe_to_tensor + RT/network.py:71 conv1's pad and conv, from the frames
+    themselves: (N,H,W,3) uint8 cv2 frames -> (N,Cout,H,W) fp32 = conv3x3(reflect_pad(toTensor255(RGB)))
+    + b on vst_conv_stem_u8 (exact fp32 VALU, one fixed FMA order; the fp32 planes of the frame are never
+    written).  Shapes the kernel does not take (Cout not a multiple of 4 up to 16, W % 4 != 0) go
+    through frames_to_tensor + conv2d."""
+    if frames.dim() != 4 or frames.shape[-1] != 3:
+        raise VstError(f"frames must be (N,H,W,3) uint8, got {tuple(frames.shape)}")
+    N, H, W, _ = frames.shape
+    fp = _ptr_u8(frames, "frames")
+    w = w.detach().contiguous()
+    Cout = w.shape[0]
+    if tuple(w.shape) != (Cout, 3, 3, 3) or (b is not None and tuple(b.shape) != (Cout,)):
+        raise VstError(f"conv_stem_u8: frames{tuple(frames.shape)} w{tuple(w.shape)}")
+    if out is not None and tuple(out.shape) != (N, Cout, H, W):
+        raise VstError(f"conv_stem_u8: out shape {tuple(out.shape)} != {(N, Cout, H, W)}")
+    bias = b.detach().contiguous() if b is not None else None
+    if not conv_stem_u8_ok(Cout, H, W, N):
+        with torch.no_grad():
+            y = conv2d(frames_to_tensor(frames, bgr=bgr), w, bias, stride=1, pad=1, pad_mode="reflect")
+        return y if out is None else out.copy_(y)
+    if out is None:
+        out = torch.empty((N, Cout, H, W), dtype=torch.float32, device=frames.device)
+    tok = kprof.begin(2.0 * N * Cout * H * W * 27, 3.0 * N * H * W + 4.0 * (N * Cout * H * W + w.numel()),
+                      ("stem_u8", N, Cout, 3, H, W), gemm_mode())
+    lib.vst_conv_stem_u8(fp, ptr(w), ptr(bias), ptr(out), N, H, W, Cout, int(bool(bgr)), stream())
+    kprof.end(tok, family="thin")  # (a VALU kernel: outside the MFMA families' rooflines)
+    return out
+
+
 class TVSqrtFn(Function):
     """weight * mean(sqrt(clamp(dx^2 + dy^2, 1e-8))) over [:, :, :-1, :-1] (RT/train.py:57-61)."""
 

@@ -1,4 +1,5 @@
-"""Drop-in MI355X implementation of the hot-path helpers of RT/utilities.py."""
+"""Drop-in MI355X implementation of the hot-path helpers of RT/utilities.py (video inference:
+vst.rtnstv.inference, re-exported here)."""
 import os
 
 import numpy as np
@@ -7,6 +8,7 @@ import torch
 from .. import ops
 from ..metrics import TemporalError, imread, read_sintel_flow  # noqa: F401  (RT/utilities.py:113-152)
 from ..reconet.utilities import flow_warp_mask  # noqa: F401  (RT/utilities.py:80-110, same arithmetic)
+from .inference import Inference, cvframe_to_tensor  # noqa: F401  (RT/utilities.py:182-191, 296-332)
 
 
 def warp(x, flo, padding_mode="zeros"):

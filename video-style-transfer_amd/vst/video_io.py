@@ -1,4 +1,5 @@
-"""Host side of the video inference paths (vst.reconet.inference, vst.adaattn.inference): the
+"""Host side of the video inference paths (vst.reconet.inference, vst.adaattn.inference,
+vst.rtnstv.inference): the
 cv2.VideoCapture-like frame reader, the per-frame check / host resize, and the pinned staging buffer
 that uploads a chunk of uint8 frames with one async copy and turns it into fp32 planes on the device.
 """
@@ -59,8 +60,21 @@ class PinnedUploader:
         self.device, self.capacity = device, max(1, int(capacity))
         self.pinned = None
 
+    def upload_u8(self, frames):
+        """k <= capacity host frames (HxWx3 uint8) -> the same bytes, (k, H, W, 3) uint8 on the device
+        (for consumers that read the frames themselves: ops.conv_stem_u8)."""
+        dev = self._stage(frames)
+        torch.cuda.current_stream().synchronize()  # the pinned buffer is reused by the next chunk
+        return dev
+
     def upload(self, frames, bgr=True):
         """k <= capacity host frames (HxWx3 uint8) -> (k, 3, H, W) fp32 RGB planes on the device."""
+        out = ops.frames_to_tensor(self._stage(frames), bgr=bgr)
+        # the pinned buffer is reused by the next chunk: wait for this copy first
+        torch.cuda.current_stream().synchronize()
+        return out
+
+    def _stage(self, frames):
         k = len(frames)
         H, W = frames[0].shape[:2]
         shape = (max(self.capacity, k), H, W, 3)
@@ -69,8 +83,4 @@ class PinnedUploader:
         host = self.pinned[:k].numpy()
         for i, f in enumerate(frames):
             host[i] = f
-        dev = self.pinned[:k].to(self.device, non_blocking=True)
-        out = ops.frames_to_tensor(dev, bgr=bgr)
-        # the pinned buffer is reused by the next chunk: wait for this copy first
-        torch.cuda.current_stream().synchronize()
-        return out
+        return self.pinned[:k].to(self.device, non_blocking=True)
