@@ -33,10 +33,11 @@ def run(label, policy, scopes, N, Cout, Cin, H, W, rounds=5, reps=5):
     with ops.gemm_scope(scopes[0]), ops.gemm_scope(scopes[1]):
         mode = ops.gemm_role("dgrad")
         nws = ops.dgrad_exact_workspace(N, Cout, Cin, H, W, mode)
-        paths = {"padout": lambda: ops.conv_dgrad_padout(gz, w, shape, 3, 1, flops),
-                 "ring": lambda: ops.conv_dgrad_ring(gz, w, shape, 3, 1, flops)}
+        geom = (3, 1, 1, "reflect", 1)
+        paths = {"padout": lambda: ops.conv_dgrad_padout(gz, w, shape, geom, flops, mode),
+                 "ring": lambda: ops.conv_dgrad_ring(gz, w, shape, geom, flops, mode)}
         if nws >= 0:
-            paths["exact"] = lambda: ops.conv_dgrad_reflect3(gz, w, shape, flops, nws)
+            paths["exact"] = lambda: ops.conv_dgrad_reflect3(gz, w, shape, geom, flops, mode, nws=nws)
         out = {}
         for k in list(paths):
             try:

@@ -38,8 +38,8 @@ def make(shape, what):
     flops = 2.0 * N * Cout * Ho * Wo * Cin * k * k
     if what == "fwd":
         def fn():
-            ops.gemm_role("fwd")
-            return ops.conv_gemm(x, ops.packed_weight(w, False), Cout, k, Ho, Wo, gm, s, pad, up)
+            mode = ops.gemm_role("fwd")
+            return ops.conv_gemm(x, ops.packed_weight(w, False, mode), Cout, k, Ho, Wo, gm, s, pad, up, mode)
     elif what == "dgrad":
         def fn():
             return ops.conv_dgrad(gz, w, x.shape, k, s, pad, pm, up)

@@ -29,22 +29,22 @@ def main():
     for _ in range(reps):
         if which == "fwd":
             with ops.gemm_scope("stylizer"):
-                ops.gemm_role("fwd")
-                ops.conv_gemm(x, ops.packed_weight(w, False), C, 3, H, W, ops.GM_REFLECT, 1, 1, 1)
+                mode = ops.gemm_role("fwd")
+                ops.conv_gemm(x, ops.packed_weight(w, False, mode), C, 3, H, W, ops.GM_REFLECT, 1, 1, 1, mode)
         elif which.startswith("vgg"):
             scope = "stylizer" if which != "vgg3kb" else "vgg"
             with ops.gemm_scope(scope):
-                ops.gemm_role("fwd")
-                ops.conv_gemm(x, ops.packed_weight(w, False), C, 3, H, W, ops.GM_ZERO, 1, 1, 1)
+                mode = ops.gemm_role("fwd")
+                ops.conv_gemm(x, ops.packed_weight(w, False, mode), C, 3, H, W, ops.GM_ZERO, 1, 1, 1, mode)
         elif which == "dgrad":
-            ops.gemm_role("dgrad")
-            ops.conv_gemm(gy, ops.packed_weight(w, True), C, 3, H, W, ops.GM_TRANSPOSED, 1, 1, 1)
+            mode = ops.gemm_role("dgrad")
+            ops.conv_gemm(gy, ops.packed_weight(w, True, mode), C, 3, H, W, ops.GM_TRANSPOSED, 1, 1, 1, mode)
         elif which == "wgrad":
             ops.conv_wgrad(gy, x, w.shape, 3, 1, 1, "reflect", 1)
         elif which == "attn":
             from vst.adaattn.attention import bmm_at_b
             q = torch.randn(4, 448, 8192, device="cuda", generator=g)
-            bmm_at_b(q, 8192, 448, False, q, 8192)
+            bmm_at_b(q, 8192, 448, False, q, 8192, ops.gemm_role("attn"))
     torch.cuda.synchronize()
     print("done", which)
 

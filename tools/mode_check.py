@@ -19,6 +19,6 @@ for mode in ("f32", "bf16x6", "bf16x3", "bf16"):
     ops.set_gemm_mode(mode)
     y = ops.conv2d(x.cuda(), w.cuda(), None, pad=1).cpu().double()
     e = ((y - ref).abs().max() / ref.abs().max()).item()
-    z = gemm_abt(a.cuda(), b.cuda()).cpu().double()
+    z = gemm_abt(a.cuda(), b.cuda(), ops.gemm_role("attn")).cpu().double()
     e2 = ((z - refg).abs().max() / refg.abs().max()).item()
     print(f"{mode:7s} conv fwd rel err {e:.3e}   gemm_abt rel err {e2:.3e}", flush=True)

@@ -5,6 +5,7 @@ result, and the first offender is printed with its operands' ranges, role mode a
     python tools/nan_diag.py [--gemm f16] [--size 128x256]
 """
 import argparse
+import inspect
 import os
 import sys
 
@@ -41,14 +42,18 @@ def main():
             if isinstance(out, torch.Tensor) and not seen and not bool(torch.isfinite(out).all()):
                 seen.append(name)
                 rng = [(tuple(t.shape), float(t.abs().max())) for t in a if isinstance(t, torch.Tensor)]
-                print(f"first non-finite: {mod.__name__}.{name} mode {ops.gemm_mode_name(ops.gemm_mode())} "
+                mode = inspect.signature(orig).bind(*a, **k).arguments.get("mode")
+                print(f"first non-finite: {mod.__name__}.{name} mode {ops.gemm_mode_name(mode)} "
                       f"scope {ops._SCOPE[0]!r}/{ops._PSCOPE[0]!r} out {tuple(out.shape)} "
                       f"nonfinite {int((~torch.isfinite(out)).sum())}; tensor args (shape, max|x|): {rng}", flush=True)
             return out
 
         setattr(mod, name, f)
+        for table in (getattr(mod, "_DGRAD", {}), getattr(mod, "_FWD", {})):  # (the route tables hold the functions)
+            for key in [k for k, fn in table.items() if fn is orig]:
+                table[key] = f
 
-    for n in ("conv_gemm", "conv_wgrad", "conv_wgrad_up2", "conv_wgrad_rowsplit", "conv_dgrad_padout",
+    for n in ("conv_gemm", "conv_wgrad_gemm", "conv_wgrad_up2", "conv_wgrad_rowsplit", "conv_dgrad_padout",
               "conv_dgrad_phase2", "conv_dgrad_ring", "conv_dgrad_padout_kwu", "channel_sum"):
         wrap(ops, n)
     for n in ("gemm_abt", "bmm_at_b", "attn_gemm"):

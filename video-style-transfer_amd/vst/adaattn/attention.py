@@ -33,23 +33,23 @@ def _empty(shape, like):
     return torch.empty(shape, device=like.device, dtype=torch.float32)
 
 
-def packed_matrix(x, M, K, transpose, role="attn"):
-    """Per-image packed GEMM A operand from x[n] = X[K][M] (transpose=False) or X[M][K]."""
-    ops.gemm_role(role)
+def packed_matrix(x, M, K, transpose, mode):
+    """Per-image packed GEMM A operand from x[n] = X[K][M] (transpose=False) or X[M][K], for a launch in
+    `mode` (every product here takes the mode its caller looked up: mode = ops.gemm_role(role))."""
     N = x.shape[0]
     Mpad, Kpad = ops.pack_dims(M, K)
-    per = ops.pack_floats(Mpad, Kpad)
+    per = ops.pack_floats(Mpad, Kpad, mode)
     ap = _empty((N * per,), x)
-    lib.vst_pack_matrix(ptr(x), ptr(ap), N, M, K, int(transpose), Mpad, Kpad, M * K, ops.gemm_mode(), stream())
+    lib.vst_pack_matrix(ptr(x), ptr(ap), N, M, K, int(transpose), Mpad, Kpad, M * K, mode, stream())
     return ap, per
 
 
-def bmm_at_b(x, M, K, transpose, b, P, out=None, role="attn", accumulate=False):
+def bmm_at_b(x, M, K, transpose, b, P, mode, out=None, accumulate=False):
     """out[n] = Aop[n]^T-as-packed @ b[n]:  out[n][m][p] = sum_k Aop[n][k][m] b[n][k][p], where
     Aop[n][k][m] = x[n][k][m] (transpose=False) or x[n][m][k] (transpose=True); accumulate: out +=."""
     N = b.shape[0]
-    ap, abs_ = packed_matrix(x, M, K, transpose, role)
-    o = ops.conv_gemm(b.view(N, K, 1, P), ap, M, 1, 1, P, ops.GM_ZERO, 1, 0, 1, a_batch_stride=abs_,
+    ap, abs_ = packed_matrix(x, M, K, transpose, mode)
+    o = ops.conv_gemm(b.view(N, K, 1, P), ap, M, 1, 1, P, ops.GM_ZERO, 1, 0, 1, mode, a_batch_stride=abs_,
                       out=None if out is None else out.view(N, M, 1, P), epi=ops.EPI_ACCUM if accumulate else 0)
     return o.view(N, M, P)
 
@@ -67,9 +67,8 @@ def copy_cols(src, c0, C, dst=None, d0=0):
     return dst
 
 
-def gemm_abt(a, b, scale=1.0, role="attn"):
+def gemm_abt(a, b, mode, scale=1.0):
     """out[n][m][j] = scale * sum_r a[n][m][r] b[n][j][r]."""
-    ops.gemm_role(role)
     N, M, R = a.shape
     J = b.shape[1]
     if b.shape[0] != N or b.shape[2] != R:
@@ -78,8 +77,8 @@ def gemm_abt(a, b, scale=1.0, role="attn"):
     ws = _empty((lib.vst_wgrad_workspace(N, M, J, R),), a)
     from .. import kprof
 
-    tok = kprof.begin(2.0 * N * M * J * R, 4.0 * (a.numel() + b.numel() + out.numel()), ("abt", N, M, J, R), ops.gemm_mode())
-    lib.vst_gemm_abt(ptr(a), ptr(b), ptr(out), ptr(ws), N, M, J, R, float(scale), ops.gemm_mode(), stream())
+    tok = kprof.begin(2.0 * N * M * J * R, 4.0 * (a.numel() + b.numel() + out.numel()), ("abt", N, M, J, R), mode)
+    lib.vst_gemm_abt(ptr(a), ptr(b), ptr(out), ptr(ws), N, M, J, R, float(scale), mode, stream())
     kprof.end(tok, family="gemm_abt")
     return out
 
@@ -100,18 +99,18 @@ def _ones(n, like):
     return ops.constant(v)
 
 
-def attn_gemm(x, M, K, b, P, rb, cg, ra=None, rd=None, role="attn", transpose=False):
+def attn_gemm(x, M, K, b, P, rb, cg, mode, ra=None, rd=None, transpose=False):
     """out[n][m][p] = (sum_k Aop[n][k][m] b[n][k][p] + ra[n][m]) * rb[n][m] * cg[n][p] + rd[n][m] with
     Aop as in bmm_at_b (x[n] = X[K][M], or X[M][K] when transpose); rb / cg None = 1."""
     N = b.shape[0]
     rb = _ones(N * M, b) if rb is None else rb
     cg = _ones(N * P, b) if cg is None else cg
-    ap, abs_ = packed_matrix(x, M, K, transpose, role)
+    ap, abs_ = packed_matrix(x, M, K, transpose, mode)
     out = _empty((N, M, P), b)
     from .. import kprof
 
-    tok = kprof.begin(2.0 * N * M * P * K, 4.0 * (b.numel() + ap.numel() + out.numel()), ("attn", N, M, K, P), ops.gemm_mode())
-    lib.vst_attn_gemm(ptr(b), ptr(ap), ptr(out), N, K, P, M, abs_, ptr(ra), ptr(rb), ptr(rd), ptr(cg), ops.gemm_mode(), stream())
+    tok = kprof.begin(2.0 * N * M * P * K, 4.0 * (b.numel() + ap.numel() + out.numel()), ("attn", N, M, K, P), mode)
+    lib.vst_attn_gemm(ptr(b), ptr(ap), ptr(out), N, K, P, M, abs_, ptr(ra), ptr(rb), ptr(rd), ptr(cg), mode, stream())
     kprof.end(tok)
     return out
 
@@ -184,20 +183,20 @@ def softmax_moments(Qm, Km, VV2, block_rows=None):
     A is the attention matrix when one block held it all (else None), C the rows per block."""
     N, d, Nc = Qm.shape
     Ns = Km.shape[2]
-    role = "attn_" + SOFTMAX
+    mode = ops.gemm_role("attn_" + SOFTMAX)
     C = _softmax_rows_per_block(N, Nc, Ns) if block_rows is None else min(int(block_rows), Nc)
     A = None
     if C == Nc:
-        S = bmm_at_b(Qm, Nc, d, False, Km, Ns, role=role)  # [N][Nc][Ns]
+        S = bmm_at_b(Qm, Nc, d, False, Km, Ns, mode=mode)  # [N][Nc][Ns]
         A, _ = attention_rows(S, SOFTMAX)
         del S
-        MV = gemm_abt(VV2, A, role=role)
+        MV = gemm_abt(VV2, A, mode=mode)
     else:
         MV = _empty((N, VV2.shape[1], Nc), VV2)
         for c0 in range(0, Nc, C):
             Cb = min(C, Nc - c0)
-            Ab = _softmax_block(Qm, Km, c0, Cb, role)
-            copy_cols(gemm_abt(VV2, Ab, role=role), 0, Cb, dst=MV, d0=c0)
+            Ab = _softmax_block(Qm, Km, c0, Cb, mode)
+            copy_cols(gemm_abt(VV2, Ab, mode=mode), 0, Cb, dst=MV, d0=c0)
     return MV, A, C
 
 
@@ -217,7 +216,7 @@ class AdaAttnFn(Function):
             raise VstError(f"adaattn: Q{tuple(Q.shape)} K{tuple(K.shape)} V{tuple(V.shape)} c{tuple(cn.shape)}")
         Q, K, V, cn = (ops._check(t, "adaattn operand", 4) for t in (Q, K, V, cn))
         Qm, Km = Q.view(N, d, Nc), K.view(N, d, Ns)
-        role = "attn_" + activation
+        mode = ops.gemm_role("attn_" + activation)
         qn = kn = S = rowsum = None
         VV2 = square_concat(V)
         if activation == COSINE:
@@ -227,9 +226,9 @@ class AdaAttnFn(Function):
             qkbar = channel_dot(Qm, v=plane_dot(Km, ks))
             c, e = _vec((N, Nc), Q), _vec((N, Nc), Q)
             lib.vst_attn_fwd_rows(ptr(qkbar), ptr(qn), ptr(c), ptr(e), N * Nc, Ns, stream())
-            A = attn_gemm(Qm, Nc, d, Km, Ns, rb=c, cg=ks, rd=e, role=role)  # [N][Nc][Ns], S never stored
+            A = attn_gemm(Qm, Nc, d, Km, Ns, rb=c, cg=ks, rd=e, mode=mode)  # [N][Nc][Ns], S never stored
             rowsum = (ks, c, e)
-            MV = gemm_abt(VV2, A, role=role)  # [N][2dv][Nc]
+            MV = gemm_abt(VV2, A, mode=mode)  # [N][2dv][Nc]
             C = Nc
         elif activation == SOFTMAX:
             MV, A, C = softmax_moments(Qm, Km, VV2, block_rows)
@@ -248,7 +247,7 @@ class AdaAttnFn(Function):
     def backward(ctx, dout):
         Q, K, V, cn, qn, kn, A, VV2, MV, ks, c, e = ctx.saved_tensors
         N, d, dv, Nc, Ns, C = ctx.dims
-        role = "attn_" + ctx.activation
+        mode = ops.gemm_role("attn_" + ctx.activation)
         if ctx.needs_input_grad[3]:
             raise VstError("adaattn: gradient w.r.t. the content features (norm_v(c_x)) is not on the reference path")
         dout = dout.contiguous()
@@ -263,22 +262,22 @@ class AdaAttnFn(Function):
             for c0 in range(0, Nc, C):
                 Cb = min(C, Nc - c0)
                 full = Cb == Nc
-                Ab = A if full and A is not None else _softmax_block(Qm, Km, c0, Cb, role)  # recomputed
+                Ab = A if full and A is not None else _softmax_block(Qm, Km, c0, Cb, mode)  # recomputed
                 dMVb = dMV if full else copy_cols(dMV, c0, Cb)
                 Qb = Qm if full else copy_cols(Qm, c0, Cb)
                 if gv:
-                    bmm_at_b(dMVb, 2 * dv, Cb, True, Ab, Ns, out=dVV2, role=role, accumulate=c0 > 0)
+                    bmm_at_b(dMVb, 2 * dv, Cb, True, Ab, Ns, out=dVV2, mode=mode, accumulate=c0 > 0)
                 if gq or gk:
-                    dS = bmm_at_b(dMVb, Cb, 2 * dv, False, VV2, Ns, role=role)  # dA  [N][Cb][Ns]
+                    dS = bmm_at_b(dMVb, Cb, 2 * dv, False, VV2, Ns, mode=mode)  # dA  [N][Cb][Ns]
                     lib.vst_softmax_rows_bwd(ptr(dS), ptr(Ab), ptr(dS), N * Cb, Ns, stream())
                     if gq:
-                        dQb = gemm_abt(Km, dS, role=role)  # [N][d][Cb]
+                        dQb = gemm_abt(Km, dS, mode=mode)  # [N][d][Cb]
                         if full:
                             dQm = dQb
                         else:
                             copy_cols(dQb, 0, Cb, dst=dQm, d0=c0)
                     if gk:
-                        bmm_at_b(Qb, d, Cb, True, dS, Ns, out=dKm, role=role, accumulate=c0 > 0)  # [N][d][Ns]
+                        bmm_at_b(Qb, d, Cb, True, dS, Ns, out=dKm, mode=mode, accumulate=c0 > 0)  # [N][d][Ns]
             dV = None
             if gv:
                 dV = _empty(V.shape, V)
@@ -286,7 +285,7 @@ class AdaAttnFn(Function):
             return (dQm.view(Q.shape) if gq else None, dKm.view(K.shape) if gk else None, dV, None, None, None)
         dQ = dK = dV = None
         if gv:
-            dVV2 = bmm_at_b(dMV, 2 * dv, Nc, True, A, Ns, role=role)  # [N][2dv][Ns]
+            dVV2 = bmm_at_b(dMV, 2 * dv, Nc, True, A, Ns, mode=mode)  # [N][2dv][Ns]
             dV = _empty(V.shape, V)
             lib.vst_square_concat_bwd(ptr(dVV2), ptr(V), ptr(dV), N, dv * Ns, stream())
             del dVV2
@@ -296,17 +295,17 @@ class AdaAttnFn(Function):
             dqn, nr, cr = _vec((N, Nc), Q), _vec((N, Nc), Q), _vec((N, Nc), Q)
             lib.vst_attn_bwd_rows(ptr(r), ptr(DA), ptr(qn), ptr(c), ptr(e), ptr(dqn), ptr(nr), ptr(cr), N * Nc, Ns,
                                   stream())
-            dS = attn_gemm(dMV, Nc, 2 * dv, VV2, Ns, rb=c, cg=ks, ra=nr, role=role)  # (dA - r) c ks
+            dS = attn_gemm(dMV, Nc, 2 * dv, VV2, Ns, rb=c, cg=ks, ra=nr, mode=mode)  # (dA - r) c ks
             if gq:
-                dQ = gemm_abt(Km, dS, role=role)  # [N][d][Nc]
+                dQ = gemm_abt(Km, dS, mode=mode)  # [N][d][Nc]
                 lib.vst_norm_grad_add(ptr(dQ), ptr(dqn), ptr(qn), ptr(Qm), N, d, Nc, stream())
                 dQ = dQ.view(Q.shape)
             if gk:
-                dK = bmm_at_b(Qm, d, Nc, True, dS, Ns, role=role)  # [N][d][Ns]
+                dK = bmm_at_b(Qm, d, Nc, True, dS, Ns, mode=mode)  # [N][d][Ns]
                 dMVc = _empty(dMV.shape, dMV)
                 lib.vst_scale_cols(ptr(dMV), ptr(c), ptr(dMVc), N, 2 * dv, Nc, stream())
-                Z = gemm_abt(dMVc, Qm, role=role)  # [N][2dv][d]
-                Y = bmm_at_b(Z, d, 2 * dv, False, VV2, Ns, role=role)  # [N][d][Ns]
+                Z = gemm_abt(dMVc, Qm, mode=mode)  # [N][2dv][d]
+                Y = bmm_at_b(Z, d, 2 * dv, False, VV2, Ns, mode=mode)  # [N][d][Ns]
                 dkn = _vec((N, Ns), K)
                 lib.vst_attn_dkn(ptr(Km), ptr(Y), ptr(plane_dot(Qm, cr)), ptr(ks), ptr(dkn), N, d, Ns, stream())
                 lib.vst_norm_grad_add(ptr(dK), ptr(dkn), ptr(kn), ptr(Km), N, d, Ns, stream())
@@ -314,12 +313,12 @@ class AdaAttnFn(Function):
         return dQ, dK, dV, None, None, None
 
 
-def _softmax_block(Qm, Km, c0, C, role):
+def _softmax_block(Qm, Km, c0, C, mode):
     """A rows c0 .. c0+C-1: softmax_rows(Q[:, :, c0:c0+C]^T K)  [N][C][Ns]."""
     N, d, Nc = Qm.shape
     Ns = Km.shape[2]
     Qb = Qm if (c0 == 0 and C == Nc) else copy_cols(Qm, c0, C)
-    S = bmm_at_b(Qb, C, d, False, Km, Ns, role=role)
+    S = bmm_at_b(Qb, C, d, False, Km, Ns, mode=mode)
     A, _ = attention_rows(S, SOFTMAX)
     return A
 
@@ -411,12 +410,12 @@ def cosine_style_side(K, V):
     dv = V.shape[1]
     Km = K.view(Nk, d, -1)
     Ns = Km.shape[2]
-    role = "attn_" + COSINE
+    mode = ops.gemm_role("attn_" + COSINE)
     ks = _recip(channel_norm(Km))
     Kh = _normalized(Km, ks)
     U = _empty((Nk, 2 * dv, Ns), V)
     lib.vst_square_concat(ptr(V), ptr(U), Nk, dv * Ns, stream())
-    G = gemm_abt(Kh, U, role=role)
+    G = gemm_abt(Kh, U, mode=mode)
     return Kh, ks, U, G, plane_dot(Kh), plane_dot(U)
 
 
@@ -432,7 +431,8 @@ def cosine_content_side(Q, qn, Qh, cn, G, ksum, us, Ns):
     rinv = _empty(qk.shape, qk)
     lib.vst_attn_fwd_rows(ptr(qk), ptr(qn), ptr(_empty(qk.shape, qk)), ptr(rinv), qk.numel(), Ns,
                           stream())                     # 1 / rs = 1 / (q . ksum / ||q|| + Ns)
-    MV = attn_gemm(Gr, 2 * dv, d, Qh, Nc, rb=None, cg=rinv, ra=usr, role="attn_" + COSINE)  # (G^T qh + us) / rs
+    mode = ops.gemm_role("attn_" + COSINE)
+    MV = attn_gemm(Gr, 2 * dv, d, Qh, Nc, rb=None, cg=rinv, ra=usr, mode=mode)  # (G^T qh + us) / rs
     out = _empty((Nq, dv, h, w), cn)
     lib.vst_adaattn_out(ptr(MV), ptr(cn), ptr(out), Nq, dv * Nc, stream())
     return out, MV, rinv, Gr, ksr
@@ -464,26 +464,26 @@ class LinearCosineAttnFn(Function):
         V, cn, Qh, Kh, qs, ks, U, Gr, ksr, MV, rinv = ctx.saved_tensors
         Nq, Nk, d, dv, Nc, Ns, hw, hws = ctx.dims
         r = Nq // Nk
-        role = "attn_" + COSINE
+        mode = ops.gemm_role("attn_" + COSINE)
         if ctx.needs_input_grad[3]:
             raise VstError("adaattn: gradient w.r.t. the content features (norm_v(c_x)) is not on the reference path")
         dRh = _empty(MV.shape, MV)                          # dMV / rs, in the out-backward's pass
         lib.vst_adaattn_out_bwd_scaled(ptr(dout.contiguous()), ptr(MV), ptr(cn), ptr(rinv), ptr(dRh), Nq, dv * Nc, Nc,
                                        stream())
         te = channel_dot(dRh, y=MV)                         # rs^-1 sum_v dMV MV
-        dG = _sum_repeats(gemm_abt(Qh, dRh, role=role), r)  # [Nk][d][2dv]
+        dG = _sum_repeats(gemm_abt(Qh, dRh, mode=mode), r)  # [Nk][d][2dv]
         dQ = dK = dV = None
         if ctx.needs_input_grad[0]:
-            dQh = bmm_at_b(Gr, d, 2 * dv, True, dRh, Nc, role=role)  # G dRh  [Nq][d][Nc]
+            dQh = bmm_at_b(Gr, d, 2 * dv, True, dRh, Nc, mode=mode)  # G dRh  [Nq][d][Nc]
             _axpy(dQh, u=ksr, v=te, alpha=-1.0)
             dQ = _normalize_bwd(Qh, dQh, qs).view(Nq, d, *hw)
         if ctx.needs_input_grad[1]:
             dks = _sum_repeats(plane_dot(Qh, te), r)       # -dksum
-            dKh = attn_gemm(dG, d, 2 * dv, U, Ns, rb=None, cg=None, ra=_neg(dks), role=role, transpose=True)  # dG U + dksum
+            dKh = attn_gemm(dG, d, 2 * dv, U, Ns, rb=None, cg=None, ra=_neg(dks), mode=mode, transpose=True)  # dG U + dksum
             dK = _normalize_bwd(Kh, dKh, ks).view(Nk, d, *hws)
         if ctx.needs_input_grad[2]:
             dus = _sum_repeats(plane_dot(dRh), r)          # [Nk][2dv]
-            dU = attn_gemm(dG, 2 * dv, d, Kh, Ns, rb=None, cg=None, ra=dus, role=role)  # dG^T Kh + dus
+            dU = attn_gemm(dG, 2 * dv, d, Kh, Ns, rb=None, cg=None, ra=dus, mode=mode)  # dG^T Kh + dus
             dV = _empty(V.shape, V)
             lib.vst_square_concat_bwd(ptr(dU), ptr(V), ptr(dV), Nk, dv * Ns, stream())
         return dQ, dK, dV, None

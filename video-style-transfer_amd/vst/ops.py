@@ -53,10 +53,12 @@ KBLOCK_UP2 = KBLOCK_ON and os.environ.get("VST_KBLOCK_UP2", "1") != "0"  # A/B: 
 # step's conv1 InstanceNorm-weight gradient past its bar under bf16x6 (margin 1.05); its data gradient
 # (ConvTanh's, in the backward) takes the 9 x 1 halo form
 KBLOCK_KWU = KBLOCK_ON and os.environ.get("VST_KBLOCK_KWU", "0") != "0"
-# The C ABI is stateless: every GEMM / pack entry takes its arithmetic mode as an argument.  This
-# module chooses that argument per call from a named policy (base mode + per-role overrides,
-# optionally per model scope); _CUR holds the mode chosen by the latest gemm_role() call, which
-# the pack and GEMM calls that follow it pass to the library.
+# The C ABI is stateless: every GEMM / pack entry takes its arithmetic mode as an argument, and so
+# does everything here that packs, sizes a pack, queries a workspace, launches or records a profiler
+# token.  A caller looks the mode up once -- mode = gemm_role(role): a named policy (base mode +
+# per-role overrides, optionally per model scope) in, the mode with its KBLOCK bit out -- or-s in the
+# flags of its one launch (KBLOCK, PERTAP) and passes that one value to the pack and to the launch that
+# reads the pack.  Nothing holds a "current" mode.
 class _ThreadSlot(threading.local):
     """One value per host thread, indexed like the one-element lists it replaces (slot[0])."""
 
@@ -71,10 +73,6 @@ class _ThreadSlot(threading.local):
 
 
 _BASE_MODE = [None]  # base mode of the selected policy (process-wide)
-# mode of the GEMM being set up (gemm_role) and the model scope: per host thread, so two threads
-# issuing ops (trainers on separate streams, autograd's device thread) never pack under one mode and
-# launch under another
-_CUR = _ThreadSlot()
 # per-role overrides of the base mode; roles: "fwd" (forward products), "fwd_img" (Cin = 3),
 # "dgrad" (data gradients, Gram backward), "wgrad" (weight gradients, Gram), "attn_cosine" /
 # "attn_softmax" (AdaAttN attention products, fwd + bwd), "loss_fwd" / "loss_dgrad" (the AdaAttN
@@ -143,20 +141,11 @@ def _ensure_policy():
         use_policy(os.environ.get("VST_GEMM_POLICY", DEFAULT_POLICY))
 
 
-def base_gemm_mode():
-    """Base GEMM mode of the selected policy (0 f32, 1 bf16x3, 2 bf16, 3 bf16x6)."""
-    _ensure_policy()
-    return _BASE_MODE[0]
-
-
-def gemm_mode():
-    """The mode passed to the library by the pack / GEMM calls being issued (set by gemm_role)."""
-    _ensure_policy()
-    return _BASE_MODE[0] if _CUR[0] is None else _CUR[0]
-
-
 def gemm_mode_name(mode=None):
-    mode = base_gemm_mode() if mode is None else mode
+    """Name of `mode`'s arithmetic (default: the selected policy's base mode)."""
+    if mode is None:
+        _ensure_policy()
+        mode = _BASE_MODE[0]
     return {v: k for k, v in GEMM_MODES.items()}[mode & ~KBLOCK]
 
 
@@ -176,7 +165,7 @@ POLICY_NAME = [None]
 def set_gemm_mode(mode, policy=None):
     """mode: 0..3 or "f32"/"bf16x3"/"bf16"/"bf16x6"; policy: {role: mode} overrides (replaces GEMM_POLICY)."""
     POLICY_NAME[0] = "custom"
-    _BASE_MODE[0] = _CUR[0] = _mode_id(mode)
+    _BASE_MODE[0] = _mode_id(mode)
     if policy is not None:
         GEMM_POLICY.clear()
         GEMM_POLICY.update({r: _mode_id(m) for r, m in policy.items()})
@@ -188,7 +177,7 @@ def policy_modes():
     return sorted({gemm_mode_name(m) for m in [_BASE_MODE[0], *GEMM_POLICY.values()]})
 
 
-_SCOPE = _ThreadSlot()
+_SCOPE = _ThreadSlot()  # (per host thread: trainers on separate streams, autograd's device thread)
 _PSCOPE = _ThreadSlot()  # forward scope re-entered by a backward (policy_scope)
 
 
@@ -222,15 +211,9 @@ def policy_scope(name):
 
 
 def gemm_role(role):
-    """Choose the mode for a GEMM of `role` (call before packing its A operand); the first call
+    """The mode of a GEMM of `role` here: the policy's choice under the current scope, with the KBLOCK
+    bit where the channel-blocked K order applies.  A pure lookup (nothing is stored); the first call
     applies the VST_GEMM_POLICY environment variable (default "f32")."""
-    m = role_mode(role)
-    _CUR[0] = m
-    return m
-
-
-def role_mode(role):
-    """The mode gemm_role(role) would choose here, without making it the current one."""
     _ensure_policy()
     m = None
     sc = _PSCOPE[0] if _PSCOPE[0] is not None else _SCOPE[0]
@@ -257,9 +240,9 @@ CIN3_DIRECT = os.environ.get("VST_CIN3_DIRECT", "1") != "0"  # A/B: direct VALU 
 _IN_YMASK = os.environ.get("VST_IN_YMASK", "0") != "0"  # A/B: InstanceNorm backward reads the ReLU mask from y
 
 
-def pack_floats(Mpad, Kpad):
-    """Floats of one packed A operand in the current mode (bf16x6 blocks are 96 B, others 64 B)."""
-    return Kpad * Mpad * 3 // 2 if (gemm_mode() & ~KBLOCK) == 3 else Kpad * Mpad
+def pack_floats(Mpad, Kpad, mode):
+    """Floats of one packed A operand in `mode` (bf16x6 blocks are 96 B, others 64 B)."""
+    return Kpad * Mpad * 3 // 2 if (mode & ~KBLOCK) == 3 else Kpad * Mpad
 
 
 def pack_dims(M, K):
@@ -281,10 +264,10 @@ def _cache_entry(w):
     return {}
 
 
-def packed_weight(w, transposed, split_kh=False, kwu=False):
-    """Tap-major A[k][m] pack of a conv weight (split_kh: rows (co, kh), k = (kw, ci); kwu: over a
-    kw-unfolded source, k = kh*Cu + c*K + kw)."""
-    key = (w._version, w.data_ptr(), tuple(w.shape), bool(transposed), bool(split_kh), bool(kwu), gemm_mode())
+def packed_weight(w, transposed, mode, split_kh=False, kwu=False):
+    """Tap-major A[k][m] pack of a conv weight for a launch in `mode` (split_kh: rows (co, kh),
+    k = (kw, ci); kwu: over a kw-unfolded source, k = kh*Cu + c*K + kw)."""
+    key = (w._version, w.data_ptr(), tuple(w.shape), bool(transposed), bool(split_kh), bool(kwu), mode)
     if not w.requires_grad:
         hit = _cache_entry(w).get(key)
         if hit is not None:
@@ -305,12 +288,12 @@ def packed_weight(w, transposed, split_kh=False, kwu=False):
     else:
         M, K = (Cin, KH * KW * Cout) if transposed else (Cout, KH * KW * Cin)
     Mpad, Kpad = pack_dims(M, K)
-    out = _empty((pack_floats(Mpad, Kpad),), w)
+    out = _empty((pack_floats(Mpad, Kpad, mode),), w)
     inject_delay("pack")
     if kwu:
-        lib.vst_pack_weight_kwu(ptr(w), ptr(out), Cout, Cin, KW, Cu, int(transposed), Mpad, Kpad, gemm_mode(), stream())
+        lib.vst_pack_weight_kwu(ptr(w), ptr(out), Cout, Cin, KW, Cu, int(transposed), Mpad, Kpad, mode, stream())
     else:
-        lib.vst_pack_weight(ptr(w), ptr(out), Cout, Cin, KH, KW, int(transposed), int(split_kh), Mpad, Kpad, gemm_mode(),
+        lib.vst_pack_weight(ptr(w), ptr(out), Cout, Cin, KH, KW, int(transposed), int(split_kh), Mpad, Kpad, mode,
                             stream())
     if not w.requires_grad:
         entry = {k: v for k, v in _cache_entry(w).items() if k[0] == key[0] and k[1] == key[1]}
@@ -352,22 +335,22 @@ def conv_out_hw(H, W, ks, stride, pad, up):
     return (H * up + 2 * pad - ks) // stride + 1, (W * up + 2 * pad - ks) // stride + 1
 
 
-def conv_gemm(src, wpack, M, ks, Ho, Wo, gmode, stride, pad, up, epi=0, bias=None, out=None, aux=None, gmask=None,
+def conv_gemm(src, wpack, M, ks, Ho, Wo, gmode, stride, pad, up, mode, epi=0, bias=None, out=None, aux=None,
               a_batch_stride=0, mask=None, algo_flops=None, kh=None, pad_x=None):
-    """ks: kernel width; kh: kernel height (defaults to ks); pad_x: column padding (defaults to pad)."""
+    """mode: the GEMM mode wpack was packed in; ks: kernel width; kh: kernel height (defaults to ks);
+    pad_x: column padding (defaults to pad)."""
     N, Cs, Hs, Ws = src.shape
     kh = ks if kh is None else kh
     if out is None:
         out = _empty((N, M, Ho, Wo), src)
     pad_x = pad if pad_x is None else pad_x
-    mode = gemm_mode()
     ws, nws = splitk_workspace(src, N, Cs, M, Ho, Wo, kh, ks, gmode, stride, pad, pad_x, up, epi, a_batch_stride, mode)
     tok = kprof.begin(algo_flops if algo_flops is not None else 2.0 * N * M * Ho * Wo * Cs * ks * kh,
                       4.0 * (src.numel() + wpack.numel() + out.numel()),
                       (N, Cs, Hs, Ws, M, Ho, Wo, kh, ks, gmode, stride, pad, up), mode)
     lib.vst_conv_gemm_padx(ptr(src), ptr(wpack), ptr(bias), ptr(mask), ptr(out), N, Cs, Hs, Ws, M, kh * ks * Cs, Ho,
-                           Wo, kh, ks, gmode, stride, pad, pad_x, up, epi, a_batch_stride, ptr(aux), ptr(gmask), ptr(ws),
-                           nws, mode, stream())
+                           Wo, kh, ks, gmode, stride, pad, pad_x, up, epi, a_batch_stride, ptr(aux), None, ptr(ws), nws,
+                           mode, stream())
     kprof.end(tok)
     return out
 
@@ -391,49 +374,82 @@ def splitk_workspace(like, *geom):
     return _empty(((nb + 3) // 4,), like), nb
 
 
-def conv_dgrad(gz, w, x_shape, ks, stride, pad, pad_mode, up, gmask=None, dmask=None):
-    """Input gradient of (upsample x`up` -> pad -> conv(stride)) given the conv-output grad gz;
-    dmask: multiply the result by (dmask > 0) in the GEMM epilogue (zero-pad path, and the
-    stride-1 reflect-pad paths: the 3x3 exact-grid launch, the padded grid with its border fold)."""
-    gemm_role("dgrad")
-    N, Cin, H, W = x_shape
-    Cout = w.shape[0]
-    Ho, Wo = gz.shape[2:]
-    flops = 2.0 * N * Cout * Ho * Wo * Cin * ks * ks
-    if (pad_mode == "zero" and up == 1 and stride == 1 and dmask is None and gmask is None and Cin % 16 != 0
-            and Cin * ks * ks <= 32 and (H, W) == tuple(gz.shape[2:])):
-        # few input channels (VGG conv1_1): tap-split 1x1 GEMM (rows (c, kh, kw)) + shift-sum
-        P = conv_gemm(gz, packed_weight(w.view(Cout, Cin * ks * ks, 1, 1), transposed=True), Cin * ks * ks, 1, H, W,
-                      GM_ZERO, 1, 0, 1, algo_flops=flops)
-        dx = _empty(x_shape, gz)
-        lib.vst_tapsum(ptr(P), ptr(dx), N, Cin, H, W, ks, pad, 0, stream())
-        return dx
-    if thin_dgrad_ok(Cout, Cin, ks, stride, pad, up, W) and gmask is None:
-        return conv_dgrad_thin(gz, w, x_shape, pad_mode == "reflect", dmask)
+def conv_dgrad_route(N, Cin, Cout, H, W, Ho, Wo, ks, wk, stride, pad, pad_mode, up, masked, mode):
+    """(route, workspace bytes) of the data gradient of one conv: which launch function conv_dgrad
+    dispatches to, from the geometry (wk: the weight's (KH, KW)), whether a ReLU mask is fused
+    (`masked`), the mode and this module's A/B switches alone -- nothing is allocated or launched (the
+    bytes, of "reflect3" only, are host arithmetic of the library).  Raises on the two geometries that
+    have no route."""
+    if (pad_mode == "zero" and up == 1 and stride == 1 and not masked and Cin % 16 != 0 and Cin * ks * ks <= 32
+            and (H, W) == (Ho, Wo)):
+        return "tapsum", 0  # few input channels (VGG conv1_1)
+    if thin_dgrad_ok(Cout, Cin, ks, stride, pad, up, W):
+        return "thin", 0
     if pad_mode == "zero" and up == 1:
-        return conv_gemm(gz, packed_weight(w, transposed=True), Cin, ks, H, W, GM_TRANSPOSED, stride, pad, 1,
-                         gmask=gmask, algo_flops=flops, epi=EPI_MASK if dmask is not None else 0,
-                         mask=dmask.contiguous() if dmask is not None else None)
-    padout = pad_mode == "reflect" and stride == 1 and up == 1 and gmask is None and 0 < pad < min(H, W)
-    if dmask is not None and not padout:
+        return "zero", 0
+    padout = pad_mode == "reflect" and stride == 1 and up == 1 and 0 < pad < min(H, W)
+    if masked and not padout:
         raise VstError("dgrad: fused ReLU mask only on the zero-pad and stride-1 reflect-pad paths")
     if pad_mode != "reflect":
         raise VstError("dgrad: zero padding with upsampling is not on the reference path")
     if stride == 2 and up == 1:
-        return conv_dgrad_phase2(gz, w, x_shape, ks, pad, gmask, flops)
+        return "phase2", 0
     if padout:
-        dm = dmask.contiguous() if dmask is not None else None
-        if kwu_ok(Cout, ks, stride, up, _round4(W + 2 * pad)) and w.shape[2] == ks:
-            return conv_dgrad_padout_kwu(gz, w, x_shape, ks, pad, flops, dm)
-        if ks == 3 and pad == 1 and tuple(w.shape[2:]) == (3, 3) and (gemm_mode() & 7) in DGRAD_EXACT_MODES:
-            nws = dgrad_exact_workspace(N, Cout, Cin, H, W, gemm_mode())
+        if kwu_ok(Cout, ks, stride, up, _round4(W + 2 * pad)) and wk[0] == ks:
+            return "padout_kwu", 0
+        if ks == 3 and pad == 1 and tuple(wk) == (3, 3) and (mode & 7) in DGRAD_EXACT_MODES:
+            nws = dgrad_exact_workspace(N, Cout, Cin, H, W, mode)
             if nws >= 0:
-                return conv_dgrad_reflect3(gz, w, x_shape, flops, nws, dm)
-        return conv_dgrad_padout(gz, w, x_shape, ks, pad, flops, dm)
-    if stride == 1 and gmask is None and ks % 2 == 1 and ks > 1 and pad == ks // 2 and min(H, W) * up > ks + 1:
-        return conv_dgrad_ring(gz, w, x_shape, ks, up, flops)
+                return "reflect3", nws
+        return "padout", 0
+    if stride == 1 and ks % 2 == 1 and ks > 1 and pad == ks // 2 and min(H, W) * up > ks + 1:
+        return "ring", 0
+    return "fold", 0
+
+
+def conv_dgrad(gz, w, x_shape, ks, stride, pad, pad_mode, up, mode=None, dmask=None):
+    """Input gradient of (upsample x`up` -> pad -> conv(stride)) given the conv-output grad gz, in
+    `mode` (default: the "dgrad" role's, looked up here); dmask: multiply the result by (dmask > 0) in
+    the GEMM epilogue (zero-pad path, and the stride-1 reflect-pad paths: the 3x3 exact-grid launch, the
+    padded grid with its border fold)."""
+    mode = gemm_role("dgrad") if mode is None else mode
+    N, Cin, H, W = x_shape
+    Cout = w.shape[0]
+    Ho, Wo = gz.shape[2:]
+    route, nws = conv_dgrad_route(N, Cin, Cout, H, W, Ho, Wo, ks, tuple(w.shape[2:]), stride, pad, pad_mode, up,
+                                  dmask is not None, mode)
+    dm = dmask.contiguous() if dmask is not None else None
+    flops = 2.0 * N * Cout * Ho * Wo * Cin * ks * ks
+    return _DGRAD[route](gz, w, x_shape, (ks, stride, pad, pad_mode, up), flops, mode, dm, nws)
+
+
+def conv_dgrad_tapsum(gz, w, x_shape, geom, flops, mode, dmask=None, nws=0):
+    """Few input channels (VGG conv1_1): tap-split 1x1 GEMM (rows (c, kh, kw)) + shift-sum."""
+    ks, stride, pad, pad_mode, up = geom
+    N, Cin, H, W = x_shape
+    Cout = w.shape[0]
+    P = conv_gemm(gz, packed_weight(w.view(Cout, Cin * ks * ks, 1, 1), True, mode), Cin * ks * ks, 1, H, W, GM_ZERO,
+                  1, 0, 1, mode, algo_flops=flops)
+    dx = _empty(x_shape, gz)
+    lib.vst_tapsum(ptr(P), ptr(dx), N, Cin, H, W, ks, pad, 0, stream())
+    return dx
+
+
+def conv_dgrad_zero(gz, w, x_shape, geom, flops, mode, dmask=None, nws=0):
+    """Zero-pad conv input gradient: the transposed GEMM on the input grid."""
+    ks, stride, pad, pad_mode, up = geom
+    _, Cin, H, W = x_shape
+    return conv_gemm(gz, packed_weight(w, True, mode), Cin, ks, H, W, GM_TRANSPOSED, stride, pad, 1, mode,
+                     algo_flops=flops, epi=EPI_MASK if dmask is not None else 0, mask=dmask)
+
+
+def conv_dgrad_fold(gz, w, x_shape, geom, flops, mode, dmask=None, nws=0):
+    """Reflect-pad conv input gradient, any geometry: the transposed GEMM over the whole padded
+    (upsampled) grid, then folded back onto the input."""
+    ks, stride, pad, pad_mode, up = geom
+    N, Cin, H, W = x_shape
     Hp, Wp = H * up + 2 * pad, W * up + 2 * pad
-    dpad = conv_gemm(gz, packed_weight(w, transposed=True), Cin, ks, Hp, Wp, GM_TRANSPOSED, stride, 0, 1, gmask=gmask,
+    dpad = conv_gemm(gz, packed_weight(w, True, mode), Cin, ks, Hp, Wp, GM_TRANSPOSED, stride, 0, 1, mode,
                      algo_flops=flops)
     dx = _empty(x_shape, gz)
     lib.vst_fold_reflect(ptr(dpad), ptr(dx), N * Cin, H, W, pad, up, 0, stream())
@@ -448,17 +464,17 @@ def thin_dgrad_ok(Cout, Cin, ks, stride, pad, up, W):
         and W % 4 == 0 and W >= 8
 
 
-def conv_dgrad_thin(gz, w, x_shape, reflect, dmask=None):
+def conv_dgrad_thin(gz, w, x_shape, geom, flops, mode, dmask=None, nws=0):
     """Data gradient of a 3x3 stride-1 pad-1 conv with <= 4 output channels (the AdaAttN decoder's last
     conv, AA/network.py:99) on vst_conv_dgrad_thin: exact fp32 VALU, the fused ReLU mask applied."""
     N, Cin, H, W = x_shape
     Cout = w.shape[0]
     dx = _empty(x_shape, gz)
+    reflect = geom[3] == "reflect"
     border = _empty((N, Cin, H + 2, W + 2), gz) if reflect else None
-    dm = dmask.contiguous() if dmask is not None else None
     tok = kprof.begin(2.0 * N * Cout * H * W * Cin * 9, 4.0 * (gz.numel() + 2 * dx.numel()),
-                      ("thin_dgrad", N, Cout, Cin, H, W), gemm_mode())
-    lib.vst_conv_dgrad_thin(ptr(gz), ptr(w.contiguous()), ptr(dm), ptr(dx), ptr(border), N, Cout, Cin, H, W,
+                      ("thin_dgrad", N, Cout, Cin, H, W), mode)  # (the role's mode: the kernel is exact fp32)
+    lib.vst_conv_dgrad_thin(ptr(gz), ptr(w.contiguous()), ptr(dmask), ptr(dx), ptr(border), N, Cout, Cin, H, W,
                             int(reflect), stream())
     kprof.end(tok, family="thin")  # (a VALU kernel: outside the MFMA families' rooflines)
     return dx
@@ -485,22 +501,22 @@ def conv_thin_fwd(x, w, b=None, reflect=True, out=None, frames=None, bgr=False):
     bias = b.detach().contiguous() if b is not None else None
     nbytes = 4.0 * (x.numel() + w.numel()) + (4.0 * N * Cout * H * W if out is not None else 0.0) \
         + (3.0 * N * H * W if frames is not None else 0.0)
-    tok = kprof.begin(2.0 * N * Cout * H * W * Cin * 9, nbytes, ("thin_fwd", N, Cout, Cin, H, W), gemm_mode())
+    tok = kprof.begin(2.0 * N * Cout * H * W * Cin * 9, nbytes, ("thin_fwd", N, Cout, Cin, H, W), None)
     lib.vst_conv_thin_fwd(ptr(x), ptr(w), ptr(bias), ptr(out), None if frames is None else _ptr_u8(frames, "frames"),
                           N, Cin, H, W, Cout, int(bool(reflect)), int(bool(bgr)), stream())
     kprof.end(tok, family="thin")  # (a VALU kernel: outside the MFMA families' rooflines)
     return out if frames is None else frames
 
 
-def conv_dgrad_padout(gz, w, x_shape, ks, pad, flops, dmask=None):
+def conv_dgrad_padout(gz, w, x_shape, geom, flops, mode, dmask=None, nws=0):
     """Stride-1 reflect-pad conv input gradient: the transposed GEMM over the padded grid writes
     its interior straight into dx and its border into a side buffer, folded into dx's border band."""
+    ks, stride, pad, pad_mode, up = geom
     N, Cin, H, W = x_shape
     Cout, Ho, Wo = w.shape[0], gz.shape[2], gz.shape[3]
-    wp = packed_weight(w, transposed=True)
+    wp = packed_weight(w, True, mode)
     dx = _empty(x_shape, gz)
     border = _empty((N, Cin, H + 2 * pad, W + 2 * pad), gz)
-    mode = gemm_mode()
     ws, nws = splitk_workspace(gz, N, Cout, Cin, H + 2 * pad, W + 2 * pad, ks, ks, GM_TRANSPOSED, 1, 0, 0, 1,
                                EPI_PADOUT | (EPI_MASK if dmask is not None else 0), 0, mode)
     tok = kprof.begin(flops, 4.0 * (gz.numel() + wp.numel() + dx.numel()),
@@ -533,14 +549,13 @@ def dgrad_exact_workspace(N, Cout, Cin, H, W, mode):
     return nb
 
 
-def conv_dgrad_reflect3(gz, w, x_shape, flops, nws, dmask=None):
+def conv_dgrad_reflect3(gz, w, x_shape, geom, flops, mode, dmask=None, nws=0):
     """Stride-1 reflect-pad-1 3x3 conv input gradient on the exact grid: one halo-kernel launch, the
     reflected border's taps computed in-kernel (no border buffer, no fold)."""
     N, Cin, H, W = x_shape
     Cout = w.shape[0]
-    wp = packed_weight(w, transposed=True)
+    wp = packed_weight(w, True, mode)
     dx = _empty(x_shape, gz)
-    mode = gemm_mode()
     ws = _empty(((nws + 3) // 4,), gz) if nws > 0 and SPLITK else None
     tok = kprof.begin(flops, 4.0 * (gz.numel() + wp.numel() + dx.numel()),
                       (N, Cout, H, W, Cin, H, W, 3, 3, GM_TRANSPOSED, 1, 1, 1), mode)
@@ -553,40 +568,42 @@ def conv_dgrad_reflect3(gz, w, x_shape, flops, nws, dmask=None):
 HALO91 = os.environ.get("VST_HALO91", "1") != "0"  # A/B: ConvTanh's data gradient on the 9 x 1 halo form
 
 
-def conv_dgrad_padout_kwu(gz, w, x_shape, ks, pad, flops, dmask=None):
+def conv_dgrad_padout_kwu(gz, w, x_shape, geom, flops, mode, dmask=None, nws=0):
     """conv_dgrad_padout for a thin output gradient (ConvTanh 48->3): dy is kw-unfolded first,
     dyu[co*K + kw][y][v] = dy[co][y][v - kw] over the padded width, so the transposed GEMM is a
     Kx1 gather over 16-multiple channels."""
+    ks, stride, pad, pad_mode, up = geom
     N, Cin, H, W = x_shape
     Ho = gz.shape[2]
     dyu = unfold_kw(gz, ks, 0, -1, _round4(W + 2 * pad), reflect=False)
-    wp = packed_weight(w, True, kwu=True)
+    wp = packed_weight(w, True, mode, kwu=True)
     dx = _empty(x_shape, gz)
     border = _empty((N, Cin, H + 2 * pad, W + 2 * pad), gz)
     tok = kprof.begin(flops, 4.0 * (gz.numel() + wp.numel() + dx.numel()),
                       (N, dyu.shape[1], Ho, W + 2 * pad, Cin, H + 2 * pad, W + 2 * pad, 1, ks, GM_TRANSPOSED, 1, 0, 1),
-                      gemm_mode())
+                      mode)
     lib.vst_conv_dgrad_padout_kwu(ptr(dyu), ptr(wp), ptr(dmask), ptr(dx), ptr(border), N, dyu.shape[1], Ho, Cin, H, W,
-                                  ks, pad, gemm_mode() | (0 if HALO91 else PERTAP), stream())
+                                  ks, pad, mode | (0 if HALO91 else PERTAP), stream())
     kprof.end(tok)
     lib.vst_fold_border(ptr(border), ptr(dmask), ptr(dx), N * Cin, H, W, pad, stream())
     return dx
 
 
-def conv_dgrad_ring(gz, w, x_shape, ks, up, flops):
+def conv_dgrad_ring(gz, w, x_shape, geom, flops, mode, dmask=None, nws=0):
     """Stride-1 reflect-pad (optionally nearest-x2-upsampled) conv input gradient on the unpadded
     grid: core GEMM + the padded grid's border ring folded into dx's border band."""
+    ks, stride, pad, pad_mode, up = geom
     N, Cin, H, W = x_shape
     Cout = w.shape[0]
     p = ks // 2
     w = w.contiguous()
     if up == 1:
-        dx = conv_gemm(gz, packed_weight(w, transposed=True), Cin, ks, H, W, GM_TRANSPOSED, 1, p, 1, algo_flops=flops)
+        dx = conv_gemm(gz, packed_weight(w, True, mode), Cin, ks, H, W, GM_TRANSPOSED, 1, p, 1, mode, algo_flops=flops)
     else:
         Mpad, Kpad = pack_dims(Cin, (ks + 1) * (ks + 1) * Cout)
-        wp = _empty((pack_floats(Mpad, Kpad),), w)
-        lib.vst_pack_weight_upsum(ptr(w), ptr(wp), Cout, Cin, ks, Mpad, Kpad, gemm_mode(), stream())
-        dx = conv_gemm(gz, wp, Cin, ks + 1, H, W, GM_ZERO, 2, ks - 1 - p, 1, algo_flops=flops)
+        wp = _empty((pack_floats(Mpad, Kpad, mode),), w)
+        lib.vst_pack_weight_upsum(ptr(w), ptr(wp), Cout, Cin, ks, Mpad, Kpad, mode, stream())
+        dx = conv_gemm(gz, wp, Cin, ks + 1, H, W, GM_ZERO, 2, ks - 1 - p, 1, mode, algo_flops=flops)
     Hv, Wv = H * up, W * up
     ring = _empty((N * Cin * lib.vst_dgrad_ring_size(Hv, Wv, ks, Cout),), gz)
     lib.vst_dgrad_ring(ptr(gz), ptr(w), ptr(ring), N, Cout, Cin, ks, Hv, Wv, stream())
@@ -594,26 +611,33 @@ def conv_dgrad_ring(gz, w, x_shape, ks, up, flops):
     return dx
 
 
-def conv_dgrad_phase2(gz, w, x_shape, ks, pad, gmask=None, flops=None):
+def conv_dgrad_phase2(gz, w, x_shape, geom, flops, mode, dmask=None, nws=0):
     """Stride-2 reflect-pad conv input gradient: one transposed GEMM over the 4 parity phases of
     the padded grid (rows ci*4 + phase), interior written straight into dx, border folded after."""
+    ks, stride, pad, pad_mode, up = geom
     N, Cin, H, W = x_shape
     Cout, Ho, Wo = w.shape[0], gz.shape[2], gz.shape[3]
     k2 = (ks + 1) // 2
     Mpad, Kpad = pack_dims(4 * Cin, k2 * k2 * Cout)
-    wp = _empty((pack_floats(Mpad, Kpad),), w)
-    lib.vst_pack_weight_phase2(ptr(w.contiguous()), ptr(wp), Cout, Cin, ks, Mpad, Kpad, gemm_mode(), stream())
+    wp = _empty((pack_floats(Mpad, Kpad, mode),), w)
+    lib.vst_pack_weight_phase2(ptr(w.contiguous()), ptr(wp), Cout, Cin, ks, Mpad, Kpad, mode, stream())
     dx = _empty(x_shape, gz)
     border = _empty((N, Cin, H + 2 * pad, W + 2 * pad), gz)
     Hc, Wc = (H + 2 * pad + 1) // 2, (W + 2 * pad + 1) // 2
-    tok = kprof.begin(flops if flops is not None else 2.0 * N * Cout * Ho * Wo * Cin * ks * ks,
-                      4.0 * (gz.numel() + wp.numel() + dx.numel()),
-                      (N, Cout, Ho, Wo, 4 * Cin, Hc, Wc, k2, k2, GM_TRANSPOSED, 1, 0, 1), gemm_mode())
-    lib.vst_conv_dgrad_s2(ptr(gz), ptr(wp), ptr(gmask), ptr(dx), ptr(border), N, Cout, Ho, Wo, Cin, H, W, ks, pad,
-                          gemm_mode(), stream())
+    tok = kprof.begin(flops, 4.0 * (gz.numel() + wp.numel() + dx.numel()),
+                      (N, Cout, Ho, Wo, 4 * Cin, Hc, Wc, k2, k2, GM_TRANSPOSED, 1, 0, 1), mode)
+    lib.vst_conv_dgrad_s2(ptr(gz), ptr(wp), None, ptr(dx), ptr(border), N, Cout, Ho, Wo, Cin, H, W, ks, pad, mode,
+                          stream())
     kprof.end(tok)
     lib.vst_fold_border(ptr(border), None, ptr(dx), N * Cin, H, W, pad, stream())
     return dx
+
+
+# conv_dgrad_route's names -> their launch functions: each takes (gz, w, x_shape, geom, flops, mode, dmask, nws)
+# with geom = (ks, stride, pad, pad_mode, up), and reads what its form needs
+_DGRAD = {"tapsum": conv_dgrad_tapsum, "thin": conv_dgrad_thin, "zero": conv_dgrad_zero, "phase2": conv_dgrad_phase2,
+          "padout_kwu": conv_dgrad_padout_kwu, "reflect3": conv_dgrad_reflect3, "padout": conv_dgrad_padout,
+          "ring": conv_dgrad_ring, "fold": conv_dgrad_fold}
 
 
 _WGRAD_UP2 = os.environ.get("VST_WGRAD_UP2", "1") != "0"  # A/B switch for the phase-stacked up2 path
@@ -629,19 +653,64 @@ _WGRAD_UP2 = os.environ.get("VST_WGRAD_UP2", "1") != "0"  # A/B switch for the p
 WGRAD_HALO_RES = os.environ.get("VST_WGRAD_HALO_RES", "0") != "0"  # A/B
 
 
-def conv_wgrad(gz, x, w_shape, ks, stride, pad, pad_mode, up, out=None):
-    gemm_role("wgrad")
+RS_WGRAD = os.environ.get("VST_RSW", "1") != "0"
+THIN_WGRAD = os.environ.get("VST_THIN_WGRAD", "1") != "0"  # A/B: Cout <= 4 3x3 weight gradients on the VALU kernel
+
+
+def rowsplit_ok(Cout, ks, stride, pad_mode, up):
+    """Tiny-Cout stride-1 reflect convs (ConvTanh 48->3 k9) run as row-split GEMMs."""
+    return Cout * ks <= 32 and ks > 1 and stride == 1 and pad_mode == "reflect" and up == 1
+
+
+def conv_wgrad_route(Cin, Cout, W, ks, stride, pad, pad_mode, up, mode):
+    """(route, flags, profiler family) of the weight gradient of one conv, from the geometry, the mode
+    and this module's A/B switches alone: "up2" (the phase-stacked nearest-x2 form), "rowsplit", or
+    "gemm" (vst_conv_wgrad) with the flags or-ed into its mode (PERTAP: the row-tiled kernel) and the
+    family its launch records ("thin" where the library takes its fp32 VALU kernel)."""
+    if _WGRAD_UP2 and up == 2 and ks == 3 and stride == 1 and pad == 1 and pad_mode == "reflect":
+        return "up2", 0, "wgrad"
+    # vst_conv_wgrad's own choice (csrc/wgrad_gemm.hip thin_wgrad_ok): its fp32 VALU kernel (the AdaAttN
+    # decoder's last conv, 64 -> 3)
+    thin = THIN_WGRAD and Cout <= 4 and ks == 3 and stride == 1 and up == 1 and Cin % 4 == 0 and W % 4 == 0 and W >= 8
+    # Row-split GEMMs: the tiny-Cout convs (rowsplit_ok), and 64-output 3x3 stride-1 reflect convs over
+    # >= 64 channels (the AdaAttN decoder's conv6 / conv7, AA/network.py:93-96).  Rows (co, kh) read
+    # dY[co][y - kh], columns (kw, ci) read x[ci][y][x + kw]: M = 3 Cout and J = 3 Cin instead of M = Cout
+    # and J = 9 Cin, so each dY tile feeds 3x the rows and is re-read for 3x fewer column tiles
+    # (64 x 576 -> 192 x 192 for 64 -> 64).  Except where the halo weight gradient (vst_conv_wgrad:
+    # 32-channel multiples, split-product modes) beats it (fp16 decoder conv6 1.12 vs 1.41 ms, conv7 3.6 vs
+    # 4.5 ms at config 5, tools/wgrad_bench.py): the row-split form stays for the f32 / bf16x3 modes and
+    # the widths the halo kernel does not take (csrc/wgrad_halo.hip wgrad_halo_ok: its 64-row blocks walk
+    # 32-column strips in every split-product mode, so W % 32 == 0)
+    wide = RS_WGRAD and Cout <= 64 and Cin >= 64 and ks == 3 and stride == 1 and pad_mode == "reflect" and up == 1 \
+        and W % 16 == 0 and not (Cin % 32 == 0 and W % 32 == 0 and (mode & 7) in (
+            GEMM_MODES["bf16x6"], GEMM_MODES["bf16"], GEMM_MODES["f16"]))
+    if not thin and pad == ks // 2 and (rowsplit_ok(Cout, ks, stride, pad_mode, up) or wide):
+        return "rowsplit", 0, None
+    flags = 0
+    if not WGRAD_HALO_RES and (mode & 7) == GEMM_MODES["bf16x6"] and Cout % 192 == 0 and Cout % 128 != 0:
+        flags = PERTAP
+    if not THIN_WGRAD and Cout <= 4:
+        flags = PERTAP  # (the A/B switch: the row-tiled GEMM instead of the VALU kernel)
+    return "gemm", flags, "thin" if pad == 1 and thin else "wgrad"
+
+
+def conv_wgrad(gz, x, w_shape, ks, stride, pad, pad_mode, up, mode=None, out=None):
+    """Weight gradient of (upsample x`up` -> pad -> conv(stride)) in `mode` (default: the "wgrad" role's,
+    looked up here), accumulated into `out` when given."""
+    mode = gemm_role("wgrad") if mode is None else mode
+    route, flags, family = conv_wgrad_route(x.shape[1], w_shape[0], x.shape[3], ks, stride, pad, pad_mode, up, mode)
+    if route == "up2":
+        return conv_wgrad_up2(gz, x, w_shape, mode, out)
+    if route == "rowsplit":
+        return conv_wgrad_rowsplit(gz, x, w_shape, mode, out)
+    return conv_wgrad_gemm(gz, x, w_shape, ks, stride, pad, pad_mode, up, mode | flags, family, out)
+
+
+def conv_wgrad_gemm(gz, x, w_shape, ks, stride, pad, pad_mode, up, mode, family="wgrad", out=None):
     N, Cin, H, W = x.shape
     Cout = w_shape[0]
     Ho, Wo = gz.shape[2:]
-    if _WGRAD_UP2 and up == 2 and ks == 3 and stride == 1 and pad == 1 and pad_mode == "reflect":
-        return conv_wgrad_up2(gz, x, w_shape, out)
     gm = GM_REFLECT if pad_mode == "reflect" else GM_ZERO
-    mode = gemm_mode()
-    if not WGRAD_HALO_RES and (mode & 7) == GEMM_MODES["bf16x6"] and Cout % 192 == 0 and Cout % 128 != 0:
-        mode |= PERTAP
-    if not THIN_WGRAD and Cout <= 4:
-        mode |= PERTAP  # (the A/B switch: the row-tiled GEMM instead of the VALU kernel)
     nws = lib.vst_conv_wgrad_workspace(N, Cin, H, W, Cout, Ho, Wo, ks, ks, gm, stride, pad, up, mode)
     ws = _empty((nws,), x)
     acc = out is not None
@@ -650,11 +719,11 @@ def conv_wgrad(gz, x, w_shape, ks, stride, pad, pad_mode, up, out=None):
                       ("wgrad", N, Cin, H, W, Cout, Ho, Wo, ks, stride, pad, up), mode)
     lib.vst_conv_wgrad(ptr(gz), ptr(x), ptr(dw), ptr(ws), nws, N, Cin, H, W, Cout, Ho, Wo, ks, ks, gm, stride, pad,
                        up, int(acc), mode, stream())
-    kprof.end(tok, family="thin" if pad == 1 and thin_wgrad_ok(Cout, Cin, ks, stride, up, W) else "wgrad")
+    kprof.end(tok, family=family)
     return dw
 
 
-def conv_wgrad_up2(gz, x, w_shape, out=None):
+def conv_wgrad_up2(gz, x, w_shape, mode, out=None):
     """Weight gradient of UpsampleConvLayer (nearest x2, reflect pad 1, k3; RC/network.py:114-120)
     as the phase-stacked source-grid GEMM (vst_conv_wgrad_up2)."""
     N, Cin, H, W = x.shape
@@ -663,75 +732,111 @@ def conv_wgrad_up2(gz, x, w_shape, out=None):
     acc = out is not None
     dw = _empty(w_shape, x) if out is None else out
     tok = kprof.begin(2.0 * N * Cout * 4 * H * W * Cin * 9, 4.0 * (gz.numel() + x.numel() + dw.numel()),
-                      ("wgrad_up2", N, Cin, H, W, Cout), gemm_mode())
-    lib.vst_conv_wgrad_up2(ptr(gz), ptr(x), ptr(dw), ptr(ws), N, Cin, H, W, Cout, int(acc), gemm_mode(), stream())
+                      ("wgrad_up2", N, Cin, H, W, Cout), mode)
+    lib.vst_conv_wgrad_up2(ptr(gz), ptr(x), ptr(dw), ptr(ws), N, Cin, H, W, Cout, int(acc), mode, stream())
     kprof.end(tok, family="wgrad")
     return dw
 
 
-def rowsplit_ok(Cout, ks, stride, pad_mode, up):
-    """Tiny-Cout stride-1 reflect convs (ConvTanh 48->3 k9) run as row-split GEMMs."""
-    return Cout * ks <= 32 and ks > 1 and stride == 1 and pad_mode == "reflect" and up == 1
-
-
-RS_WGRAD = os.environ.get("VST_RSW", "1") != "0"
-THIN_WGRAD = os.environ.get("VST_THIN_WGRAD", "1") != "0"  # A/B: Cout <= 4 3x3 weight gradients on the VALU kernel
-
-
-def thin_wgrad_ok(Cout, Cin, ks, stride, up, W):
-    """vst_conv_wgrad's own choice (csrc/wgrad_gemm.hip thin_wgrad_ok) for pad-1 convs"""
-    return THIN_WGRAD and Cout <= 4 and ks == 3 and stride == 1 and up == 1 and Cin % 4 == 0 and W % 4 == 0 and W >= 8
-
-
-def rowsplit_wgrad_ok(Cout, Cin, ks, stride, pad_mode, up, W):
-    """Weight gradients that run as row-split GEMMs: the tiny-Cout convs above, and 64-output
-    3x3 stride-1 reflect convs over >= 64 channels (the AdaAttN decoder's conv6 / conv7,
-    AA/network.py:93-96).  Rows (co, kh) read dY[co][y - kh], columns (kw, ci) read x[ci][y][x + kw]:
-    M = 3 Cout and J = 3 Cin instead of M = Cout and J = 9 Cin, so each dY tile feeds 3x the rows and
-    is re-read for 3x fewer column tiles (64 x 576 -> 192 x 192 for 64 -> 64)."""
-    if thin_wgrad_ok(Cout, Cin, ks, stride, up, W):
-        return False  # vst_conv_wgrad's fp32 VALU kernel (the AdaAttN decoder's last conv, 64 -> 3)
-    if rowsplit_ok(Cout, ks, stride, pad_mode, up):
-        return True
-    if not (RS_WGRAD and Cout <= 64 and Cin >= 64 and ks == 3 and stride == 1 and pad_mode == "reflect" and up == 1
-            and W % 16 == 0):
-        return False
-    # the halo weight gradient (vst_conv_wgrad: 32-channel multiples, split-product modes) beats the
-    # row-split GEMM on these shapes (fp16 decoder conv6 1.12 vs 1.41 ms, conv7 3.6 vs 4.5 ms at config 5,
-    # tools/wgrad_bench.py); the row-split form stays for the f32 / bf16x3 modes and the widths the halo
-    # kernel does not take (csrc/wgrad_halo.hip wgrad_halo_ok: its 64-row blocks walk 32-column strips
-    # in every split-product mode, so W % 32 == 0)
-    return not (Cin % 32 == 0 and W % 32 == 0 and (role_mode("wgrad") & 7) in (
-        GEMM_MODES["bf16x6"], GEMM_MODES["bf16"], GEMM_MODES["f16"]))
+def conv_wgrad_rowsplit(gz, x, w_shape, mode, out=None):
+    N, Cin, H, W = x.shape
+    Cout, _, K, _ = w_shape
+    ws = _empty((lib.vst_wgrad_workspace(N, Cout * K, K * Cin, (H + K - 1) * W),), x)
+    acc = out is not None
+    dw = _empty(w_shape, x) if out is None else out
+    lib.vst_conv_wgrad_rowsplit(ptr(gz), ptr(x), ptr(dw), ptr(ws), N, Cin, H, W, Cout, K, int(acc), mode, stream())
+    return dw
 
 
 KBLOCK_RS = KBLOCK_ON and os.environ.get("VST_KBLOCK_RS", "1") != "0"  # A/B: the row-split forward blocked
 
 
-def conv_fwd_rowsplit(x, w, b, epi, aux):
+def conv_fwd_route(Cin, Cout, H, W, ks, stride, pad, pad_mode, up, act):
+    """The form the forward of one conv takes ("rowsplit", "cin3", "up2", "kwu" or "gemm": _FWD's launch
+    functions), from the geometry and this module's A/B switches alone."""
+    if rowsplit_ok(Cout, ks, stride, pad_mode, up) and pad == ks // 2:
+        return "rowsplit"
+    if CIN3_DIRECT and Cin == 3 and ks == 3 and stride == 1 and up == 1 and pad == 1 and act in (None, "relu") \
+            and H > 1 and W > 1:
+        return "cin3"
+    if UP2_FWD and up == 2 and ks == 3 and stride == 1 and pad == 1 and pad_mode == "reflect" and act is None:
+        return "up2"
+    if kwu_ok(Cin, ks, stride, up, W) and 0 < pad < min(H, W) and conv_out_hw(H, W, ks, stride, pad, up) == (H, W):
+        return "kwu"
+    return "gemm"
+
+
+# The forward launch functions: each takes (x, w, bias, epi, aux, geom, mode), geom = (stride, pad, pad_mode, up, act)
+def conv_fwd_rowsplit(x, w, b, epi, aux, geom, mode):
     N, Cin, H, W = x.shape
     Cout, _, K, _ = w.shape
     Hq = H + K - 1
     # the 1 x K GEMM in the channel-blocked K order: the halo kernel's 1 x 9 form (the source rows
     # staged once per 16-channel block for the nine column taps)
     if KBLOCK_RS and Cin % 16 == 0:
-        _CUR[0] |= KBLOCK
-    P = conv_gemm(x, packed_weight(w, False, split_kh=True), Cout * K, K, Hq, W, GM_REFLECT, 1, K // 2, 1, kh=1,
-                  algo_flops=2.0 * N * Cout * H * W * Cin * K * K)
+        mode |= KBLOCK
+    P = conv_gemm(x, packed_weight(w, False, mode, split_kh=True), Cout * K, K, Hq, W, GM_REFLECT, 1, K // 2, 1, mode,
+                  kh=1, algo_flops=2.0 * N * Cout * H * W * Cin * K * K)
     out = _empty((N, Cout, H, W), x)
     lib.vst_rowsplit_reduce(ptr(P), ptr(b), ptr(out), ptr(aux), N, Cout, K, H, W, epi, stream())
     return out
 
 
-def conv_wgrad_rowsplit(gz, x, w_shape, out=None):
-    gemm_role("wgrad")
+def conv_fwd_cin3(x, w, b, epi, aux, geom, mode):
+    """VGG conv1_1: 27 MACs per output, bound by the output write -> direct fp32 VALU kernel."""
+    N, _, H, W = x.shape
+    Cout = w.shape[0]
+    out = _empty((N, Cout, H, W), x)
+    lib.vst_conv_cin3_k3(ptr(x), ptr(w), ptr(b), ptr(out), N, H, W, Cout, int(geom[2] == "reflect"),
+                         int(geom[4] == "relu"), stream())
+    return out
+
+
+def conv_fwd_up2(x, w, b, epi, aux, geom, mode):
+    """UpsampleConvLayer: phase-stacked 2x2 GEMM on the source grid (tap-summed weights), in the
+    channel-blocked K order (the halo-tiled kernel's 2x2 form)."""
     N, Cin, H, W = x.shape
-    Cout, _, K, _ = w_shape
-    ws = _empty((lib.vst_wgrad_workspace(N, Cout * K, K * Cin, (H + K - 1) * W),), x)
-    acc = out is not None
-    dw = _empty(w_shape, x) if out is None else out
-    lib.vst_conv_wgrad_rowsplit(ptr(gz), ptr(x), ptr(dw), ptr(ws), N, Cin, H, W, Cout, K, int(acc), gemm_mode(), stream())
-    return dw
+    Cout = w.shape[0]
+    if KBLOCK_UP2:
+        mode |= KBLOCK
+    w2 = _empty((4 * Cout, Cin, 2, 2), w)
+    lib.vst_up2_phase_weights(ptr(w), ptr(w2), Cout, Cin, stream())
+    out = _empty((N, Cout, 2 * H, 2 * W), x)
+    wp = packed_weight(w2, False, mode)
+    tok = kprof.begin(2.0 * N * Cout * 4 * H * W * Cin * 9, 4.0 * (x.numel() + wp.numel() + out.numel()),
+                      (N, Cin, H, W, 4 * Cout, H + 1, W + 1, 2, 2, 3, 1, 1, 1), mode)
+    lib.vst_conv_up2_fwd(ptr(x), ptr(wp), ptr(b), ptr(out), N, Cin, H, W, Cout, mode, stream())
+    kprof.end(tok)
+    return out
+
+
+def conv_fwd_kwu(x, w, b, epi, aux, geom, mode):
+    """Thin input (3-channel frames): kw-unfold, then a Kx1 conv on the 16-channel k-tile path, in the
+    channel-blocked K order under VST_KBLOCK_KWU (the halo-tiled kernel's 9 x 1 form).  (The weight
+    gradient stays on x: over the unfolded input its columns pad 243 -> 384, measured 1.7x slower.)"""
+    N, Cin, H, W = x.shape
+    Cout, _, ks, _ = w.shape
+    pad, reflect = geom[1], geom[2] == "reflect"
+    if KBLOCK_KWU:
+        mode |= KBLOCK
+    xu = unfold_kw(x, ks, -pad, 1, W, reflect)
+    return conv_gemm(xu, packed_weight(w, False, mode, kwu=True), Cout, 1, H, W, GM_REFLECT if reflect else GM_ZERO, 1,
+                     pad, 1, mode, epi=epi, bias=b, aux=aux, kh=ks, pad_x=0,
+                     algo_flops=2.0 * N * Cout * H * W * Cin * ks * ks)
+
+
+def conv_fwd_gemm(x, w, b, epi, aux, geom, mode):
+    N, Cin, H, W = x.shape
+    Cout, _, ks, _ = w.shape
+    stride, pad, pad_mode, up, _ = geom
+    Ho, Wo = conv_out_hw(H, W, ks, stride, pad, up)
+    gm = GM_REFLECT if pad_mode == "reflect" else GM_ZERO
+    return conv_gemm(x, packed_weight(w, False, mode), Cout, ks, Ho, Wo, gm, stride, pad, up, mode, epi=epi, bias=b,
+                     aux=aux)
+
+
+_FWD = {"rowsplit": conv_fwd_rowsplit, "cin3": conv_fwd_cin3, "up2": conv_fwd_up2, "kwu": conv_fwd_kwu,
+        "gemm": conv_fwd_gemm}
 
 
 def channel_sum(x, out=None):
@@ -941,42 +1046,9 @@ class Conv2dFn(Function):
         # image-space inputs (3 channels: ReCoNet conv1 on raw [0, 255] frames, VGG conv1_1) have a
         # large common offset that the following InstanceNorm subtracts again: their products
         # need fp32 relative precision (role "fwd_img")
-        gemm_role("fwd_img" if Cin == 3 else "fwd")
-        if rowsplit_ok(Cout, ks, stride, pad_mode, up) and pad == ks // 2:
-            out = conv_fwd_rowsplit(x, w, bias, epi, aux)
-        elif CIN3_DIRECT and Cin == 3 and ks == 3 and stride == 1 and up == 1 and pad == 1 and act in (None, "relu") \
-                and H > 1 and W > 1:
-            # VGG conv1_1: 27 MACs per output, bound by the output write -> direct fp32 VALU kernel
-            out = _empty((N, Cout, Ho, Wo), x)
-            lib.vst_conv_cin3_k3(ptr(x), ptr(w), ptr(bias), ptr(out), N, H, W, Cout, int(pad_mode == "reflect"),
-                                 int(act == "relu"), stream())
-        elif UP2_FWD and up == 2 and ks == 3 and stride == 1 and pad == 1 and pad_mode == "reflect" and act is None:
-            # UpsampleConvLayer: phase-stacked 2x2 GEMM on the source grid (tap-summed weights), in
-            # the channel-blocked K order (the halo-tiled kernel's 2x2 form)
-            if KBLOCK_UP2:
-                _CUR[0] |= KBLOCK
-            w2 = _empty((4 * Cout, Cin, 2, 2), w)
-            lib.vst_up2_phase_weights(ptr(w), ptr(w2), Cout, Cin, stream())
-            out = _empty((N, Cout, Ho, Wo), x)
-            wp = packed_weight(w2, False)
-            tok = kprof.begin(2.0 * N * Cout * Ho * Wo * Cin * ks * ks, 4.0 * (x.numel() + wp.numel() + out.numel()),
-                              (N, Cin, H, W, 4 * Cout, H + 1, W + 1, 2, 2, 3, 1, 1, 1), gemm_mode())
-            lib.vst_conv_up2_fwd(ptr(x), ptr(wp), ptr(bias), ptr(out), N, Cin, H, W, Cout, gemm_mode(), stream())
-            kprof.end(tok)
-        elif kwu_ok(Cin, ks, stride, up, W) and 0 < pad < min(H, W) and Ho == H and Wo == W:
-            # thin input (3-channel frames): kw-unfold, then a Kx1 conv on the 16-channel k-tile path, in
-            # the channel-blocked K order (the halo-tiled kernel's 9 x 1 form)
-            if KBLOCK_KWU:
-                _CUR[0] |= KBLOCK
-            xu = unfold_kw(x, ks, -pad, 1, W, pad_mode == "reflect")
-            out = conv_gemm(xu, packed_weight(w, False, kwu=True), Cout, 1, Ho, Wo,
-                            GM_REFLECT if pad_mode == "reflect" else GM_ZERO, 1, pad, 1, epi=epi, bias=bias, aux=aux,
-                            kh=ks, pad_x=0, algo_flops=2.0 * N * Cout * Ho * Wo * Cin * ks * ks)
-            # (the weight gradient stays on x: over the unfolded input its columns pad 243 -> 384,
-            # measured 1.7x slower)
-        else:
-            out = conv_gemm(x, packed_weight(w, False), Cout, ks, Ho, Wo, GM_REFLECT if pad_mode == "reflect" else GM_ZERO,
-                            stride, pad, up, epi=epi, bias=bias, aux=aux)
+        mode = gemm_role("fwd_img" if Cin == 3 else "fwd")
+        route = conv_fwd_route(Cin, Cout, H, W, ks, stride, pad, pad_mode, up, act)
+        out = _FWD[route](x, w, bias, epi, aux, (stride, pad, pad_mode, up, act), mode)
         ctx.geom = (ks, stride, pad, pad_mode, up, act)
         ctx.scope = _SCOPE[0]
         ctx.relu_flags = (bool(mask_dx), bool(premasked))
@@ -995,7 +1067,7 @@ class Conv2dFn(Function):
         x, w, y, t = ctx.saved_tensors
         ks, stride, pad, pad_mode, up, act = ctx.geom
         gy = gy.contiguous()
-        gz, gmask = gy, None
+        gz = gy
         if act == "tanh":
             gz = _empty(gy.shape, gy)
             lib.vst_tanh_out_bwd(ptr(gy), ptr(t), ptr(gz), gy.numel(), gy[0, 0].numel(), 0, stream())
@@ -1006,16 +1078,13 @@ class Conv2dFn(Function):
             lib.vst_relu_bwd(ptr(gy), ptr(y), ptr(gz), gy.numel(), stream())
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = conv_dgrad(gz, w, x.shape, ks, stride, pad, pad_mode, up, gmask=gmask,
+            dx = conv_dgrad(gz, w, x.shape, ks, stride, pad, pad_mode, up, gemm_role("dgrad"),
                             dmask=x if ctx.relu_flags[0] else None)
         if ctx.needs_input_grad[1]:
             sink = grad_sink(ctx.params[0])
-            if rowsplit_wgrad_ok(w.shape[0], w.shape[1], ks, stride, pad_mode, up, x.shape[3]) and pad == ks // 2:
-                dw = wgrad_into_sink(lambda: conv_wgrad_rowsplit(gz, x, w.shape, out=sink), sink, gz, x,
-                                     overlap=ctx.needs_input_grad[0])
-            else:
-                dw = wgrad_into_sink(lambda: conv_wgrad(gz, x, w.shape, ks, stride, pad, pad_mode, up, out=sink),
-                                     sink, gz, x, overlap=ctx.needs_input_grad[0])
+            mode = gemm_role("wgrad")
+            dw = wgrad_into_sink(lambda: conv_wgrad(gz, x, w.shape, ks, stride, pad, pad_mode, up, mode, out=sink),
+                                 sink, gz, x, overlap=ctx.needs_input_grad[0])
             dw = None if sink is not None else dw
         if ctx.has_bias and ctx.needs_input_grad[2]:
             sink = grad_sink(ctx.params[1])
@@ -1223,9 +1292,8 @@ class GramFn(Function):
         N, C, H, W = y.shape
         g = _empty((N, C, C), y)
         ws = _empty((lib.vst_wgrad_workspace(N, C, C, H * W),), y)
-        gemm_role("fwd")
         ctx.scale = 1.0 / (H * W) if per_hw else 1.0 / (C * H * W)
-        lib.vst_gram(ptr(y), ptr(g), ptr(ws), N, C, H * W, ctx.scale, gemm_mode(), stream())
+        lib.vst_gram(ptr(y), ptr(g), ptr(ws), N, C, H * W, ctx.scale, gemm_role("fwd"), stream())
         ctx.save_for_backward(y)
         return g
 
@@ -1233,11 +1301,12 @@ class GramFn(Function):
     def backward(ctx, gg):
         (y,) = ctx.saved_tensors
         N, C, H, W = y.shape
-        gemm_role("dgrad")  # before sizing S: the pack layout (and size) is the dgrad role's mode
+        mode = gemm_role("dgrad")  # (outside the forward's policy_scope, as ConvTranspose2dFn.backward)
         Mpad, Kpad = pack_dims(C, C)
-        S = _empty((N * pack_floats(Mpad, Kpad),), y)
-        lib.vst_symmetrize(ptr(gg.contiguous()), ptr(S), N, C, Kpad, Mpad, ctx.scale, gemm_mode(), stream())
-        dy = conv_gemm(y.view(N, C, 1, H * W), S, C, 1, 1, H * W, GM_ZERO, 1, 0, 1, a_batch_stride=pack_floats(Mpad, Kpad))
+        per = pack_floats(Mpad, Kpad, mode)
+        S = _empty((N * per,), y)
+        lib.vst_symmetrize(ptr(gg.contiguous()), ptr(S), N, C, Kpad, Mpad, ctx.scale, mode, stream())
+        dy = conv_gemm(y.view(N, C, 1, H * W), S, C, 1, 1, H * W, GM_ZERO, 1, 0, 1, mode, a_batch_stride=per)
         return dy.view(N, C, H, W), None
 
 
@@ -1730,9 +1799,9 @@ class ConvTranspose2dFn(Function):
             raise VstError("conv_transpose: output size is not the transposed conv's input size")
         if bias_const is not None:
             b = bias_const
-        gemm_role("fwd")
+        mode = gemm_role("fwd")
         flops = 2.0 * N * Cin * H * W * Cout * ks * ks
-        out = conv_gemm(x, packed_weight(w, transposed=True), Cout, ks, Ho, Wo, GM_TRANSPOSED, stride, pad, 1,
+        out = conv_gemm(x, packed_weight(w, True, mode), Cout, ks, Ho, Wo, GM_TRANSPOSED, stride, pad, 1, mode,
                         epi=EPI_BIAS if b is not None else 0, bias=b.contiguous() if b is not None else None,
                         algo_flops=flops)
         ctx.geom = (ks, stride, pad)
@@ -1749,11 +1818,13 @@ class ConvTranspose2dFn(Function):
         N, Cin, H, W = x.shape
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            gemm_role("dgrad")
-            dx = conv_gemm(gy, packed_weight(w, False), Cin, ks, H, W, GM_ZERO, stride, pad, 1)
+            mode = gemm_role("dgrad")
+            dx = conv_gemm(gy, packed_weight(w, False, mode), Cin, ks, H, W, GM_ZERO, stride, pad, 1, mode)
         if ctx.needs_input_grad[1]:
             sink = grad_sink(ctx.params[0])
-            dw = wgrad_into_sink(lambda: conv_wgrad(x, gy, w.shape, ks, stride, pad, "zero", 1, out=sink), sink, x, gy)
+            wmode = gemm_role("wgrad")
+            dw = wgrad_into_sink(lambda: conv_wgrad(x, gy, w.shape, ks, stride, pad, "zero", 1, wmode, out=sink), sink,
+                                 x, gy)
             dw = None if sink is not None else dw
         if ctx.has_bias and ctx.needs_input_grad[2]:
             sink = grad_sink(ctx.params[1])
@@ -1927,7 +1998,7 @@ def conv_stem_u8(frames, w, b=None, bgr=True, out=None):
     if out is None:
         out = torch.empty((N, Cout, H, W), dtype=torch.float32, device=frames.device)
     tok = kprof.begin(2.0 * N * Cout * H * W * 27, 3.0 * N * H * W + 4.0 * (N * Cout * H * W + w.numel()),
-                      ("stem_u8", N, Cout, 3, H, W), gemm_mode())
+                      ("stem_u8", N, Cout, 3, H, W), None)
     lib.vst_conv_stem_u8(fp, ptr(w), ptr(bias), ptr(out), N, H, W, Cout, int(bool(bgr)), stream())
     kprof.end(tok, family="thin")  # (a VALU kernel: outside the MFMA families' rooflines)
     return out
