@@ -628,11 +628,34 @@ int vst_lpips_head(const float* f0, long f0_bs, const float* f1, long f1_bs, con
 /* im2tensor + ScalingLayer (AA/lpips/__init__.py:86-88, AA/lpips/lpips.py:130-135,164-171) in one pass
  * into images [batch_offset, batch_offset + N) of out ([..][3][H][W] fp32).  src_u8 = 1: src is N x H x W
  * x 3 uint8 (swap_rb: BGR frames), t = float(double(v) / 127.5 - 1.0) -- numpy's float64, then
- * torch.Tensor; src_u8 = 0: src is N x 3 x H x W fp32, t = normalize ? 2 x - 1 : x.  scaling = 1 (version
+ * torch.Tensor; src_u8 = 0: src is N x 3 x H x W fp32, t = normalize ? 2 x - 1 : x (normalize = 2: planes
+ * in [0, 255], t = 2 (x / 255) - 1, the trainers' frames).  scaling = 1 (version
  * "0.1"): out = (t - shift_c) / scale_c in fp32, shift = (-0.030, -0.088, -0.188), scale = (0.458, 0.448,
  * 0.450); scaling = 0 (version "0.0"): out = t. */
 int vst_lpips_input(const void* src, int src_u8, float* out, long batch_offset, int N, int H, int W, int swap_rb,
                     int normalize, int scaling, void* stream);
+/* The backward of vst_lpips_head for one level: gl[n] (device) is the upstream gradient of layer[n].
+ * With ra = 1 / (na + 1e-10), rb likewise, delta_c = a_c ra - b_c rb and s_c = 2 w_c delta_c gl[n] / P:
+ *   dA_c =  s_c ra - (sum_k s_k a_k) ra^2 a_c / na        (second term := 0 where na == 0)
+ *   dB_c = -s_c rb + (sum_k s_k b_k) rb^2 b_c / nb        (second term := 0 where nb == 0)
+ * At a pixel whose norm is exactly 0 autograd of the reference expression gives NaN (sqrt'(0) * 0);
+ * this entry gives the finite limit above -- the one deliberate difference.  dA goes to d0 (N images of
+ * [C][P] at d0_bs floats, like f0), dB to d1, which may be NULL (the target carries no gradient); w ==
+ * NULL means ones.  The forward's decomposition: each of f0, f1 is read from HBM once into registers,
+ * the norms are recomputed (not saved: 2 P floats per image would be written by the forward and read
+ * here to spare a reduction over registers the kernel holds anyway), the sums of squares and then the
+ * dot products meet in the forward's fixed order, d0 is written once.  No atomics, no workspace;
+ * bitwise reproducible, image n of a batch is bitwise the image alone, gl[n] = 0 gives zeros.  Limits
+ * as vst_lpips_head. */
+int vst_lpips_head_bwd(const float* f0, long f0_bs, const float* f1, long f1_bs, const float* w, const float* gl, int N,
+                       int C, long P, float* d0, long d0_bs, float* d1, long d1_bs, void* stream);
+/* The backward of vst_lpips_input's fp32 form: dx = (scaling ? dout / scale_c : dout) * gain over N x 3
+ * x H x W, gain = 1, 2 or 2 / 255 for normalize = 0, 1, 2. */
+int vst_lpips_input_bwd(const float* dout, float* dx, int N, int H, int W, int normalize, int scaling, void* stream);
+/* out[0] = weight * mean_n total[n] (summed in index order), and its backward gl[n] = g[0] * weight / N:
+ * the loss form of the distances (vst.lpips.PerceptualLoss). */
+int vst_lpips_mean(const float* total, int N, float weight, float* out, void* stream);
+int vst_lpips_mean_bwd(const float* g, int N, float weight, float* gl, void* stream);
 
 /* ---- gradient sums / fills -----------------------------------------------------------------
  * out[i] = ((a[i] + b[i]) + c[i]) + d[i] over n floats, NULL addends skipped (a..d: at least one);

@@ -7,5 +7,5 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 
-from vst.lpips import (LPIPS, NetLinLayer, ScalingLayer, im2tensor, load_image, normalize_tensor,  # noqa: E402,F401
-                       spatial_average, upsample, vgg16)
+from vst.lpips import (LPIPS, LPIPSTarget, NetLinLayer, PerceptualLoss, ScalingLayer, im2tensor,  # noqa: E402,F401
+                       load_image, normalize_tensor, spatial_average, upsample, vgg16)

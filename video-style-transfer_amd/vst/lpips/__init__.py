@@ -12,8 +12,13 @@ state_dict keys as the reference (`scaling_layer.shift`, `net.slice1.0.weight` .
     the channel sum of `lpips=False`) and the spatial mean in one pass over the two feature halves,
     the five levels summed by the kernel's accumulate flag; `spatial=True` upsamples the per-level maps
     with `ops.resize_bilinear(..., addend=...)`.
-Forward only, as the reference evaluates (`eval_mode`): inputs that require grad, `pnet_tune=True` and
-trunks other than VGG16 raise `VstError`.  Nothing synchronises with the host.
+`forward` / `forward_u8` are forward only, as the reference evaluates (`eval_mode`): inputs that require
+grad, `pnet_tune=True` and trunks other than VGG16 raise `VstError`.  Nothing synchronises with the host.
+
+As a training loss: `LPIPS.encode(in1)` caches the target's five features, `LPIPS.distance_to(target, in0)`
+is differentiable in in0 (`vgg16.forward_grad` records the trunk's data gradients, `vst_lpips_head_bwd` is
+the fused backward of the five heads, `vst_lpips_input_bwd` that of the input pass; the parameters stay
+frozen), and `PerceptualLoss` wraps both for [0,255] frames as a 0-d loss term.
 
 Weights.  The trunk takes `weights=`, a path to a local torchvision vgg16 state dict (the reference
 downloads IMAGENET1K_V1), else torchvision's default init.  The learned linear layers (1,472 floats)
@@ -31,8 +36,8 @@ from .. import ops
 from .._lib import VstError, lib, ptr, stream
 from ..reconet.network import _load_torchvision_features, run_vgg_slice, vgg_features
 
-__all__ = ["LPIPS", "ScalingLayer", "NetLinLayer", "vgg16", "normalize_tensor", "spatial_average", "upsample",
-           "im2tensor", "load_image"]
+__all__ = ["LPIPS", "LPIPSTarget", "PerceptualLoss", "ScalingLayer", "NetLinLayer", "vgg16", "normalize_tensor",
+           "spatial_average", "upsample", "im2tensor", "load_image"]
 
 # torchvision VGG16 "D" features[0:30]
 _VGG16_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512]
@@ -171,6 +176,114 @@ class vgg16(nn.Module):
                 outs.append(h)
         return VggOutputs(*outs)
 
+    def forward_grad(self, X):
+        """The same five features with autograd recorded for X (the parameters stay frozen: data
+        gradients only), built as `vst.reconet.network.Vgg16.features_upto` builds its slices: a slice
+        output is a loss feature and the next slice's pool input, so pool, gradient sum and ReLU backward
+        fuse at each boundary (`ops.feature_pool`)."""
+        outs, x = [], X
+        with ops.gemm_scope("lpips"):
+            for s in range(self.N_slices):
+                last = s == self.N_slices - 1
+                h = run_vgg_slice(getattr(self, f"slice{s + 1}"), x, skip_pool=s > 0, premasked_out=not last)
+                if not last:
+                    h, x = ops.feature_pool(h)
+                outs.append(h)
+        return VggOutputs(*outs)
+
+
+class _InputFn(torch.autograd.Function):
+    """`vst_lpips_input` over fp32 planes (normalize: 0 as is, 1 `2 x - 1`, 2 `2 (x / 255) - 1`) with its
+    backward `vst_lpips_input_bwd`."""
+
+    @staticmethod
+    def forward(ctx, x, normalize, scaling):
+        N, _, H, W = x.shape
+        out = torch.empty_like(x)
+        lib.vst_lpips_input(ptr(x), 0, ptr(out), 0, N, H, W, 0, int(normalize), int(scaling), stream())
+        ctx.args = (int(normalize), int(scaling))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        N, _, H, W = g.shape
+        dx = torch.empty_like(g)
+        lib.vst_lpips_input_bwd(ptr(g.contiguous()), ptr(dx), N, H, W, *ctx.args, stream())
+        return dx, None, None
+
+
+def _heads(feats, target, weights):
+    """The five `vst_lpips_head` calls of one trunk pass: feats / target are the two sides' five
+    features, weights five (C,) tensors or Nones.  -> (total (N,), [layer (N,)] * 5)."""
+    N, dev = feats[0].shape[0], feats[0].device
+    total = torch.empty(N, dtype=torch.float32, device=dev)
+    layers = []
+    for k, (f, t) in enumerate(zip(feats, target)):
+        C, h, w = f.shape[1:]
+        P = h * w
+        layer = torch.empty(N, dtype=torch.float32, device=dev)
+        ws = torch.empty(max(1, lib.vst_lpips_head_workspace(N, C, P) // 8), dtype=torch.float64, device=dev)
+        lib.vst_lpips_head(ptr(f), C * P, ptr(t), C * P, ptr(weights[k]), N, C, P, ptr(layer), ptr(total), int(k > 0),
+                           None, ws.data_ptr(), stream())
+        layers.append(layer)
+    return total, layers
+
+
+class _HeadsFn(torch.autograd.Function):
+    """total[n] = the sum over the five levels of `vst_lpips_head`, differentiable in the first side's
+    features: the backward launches `vst_lpips_head_bwd` per level with the total's gradient as every
+    level's `gl` and `d1 = NULL` (the target carries no gradient).  The per-level values come back
+    detached."""
+
+    @staticmethod
+    def forward(ctx, L, *tensors):
+        feats, target, weights = tensors[:L], tensors[L:2 * L], tensors[2 * L:]
+        total, layers = _heads(feats, target, weights)
+        ctx.L = L
+        ctx.save_for_backward(*tensors)
+        ctx.mark_non_differentiable(*layers)
+        return (total, *layers)
+
+    @staticmethod
+    def backward(ctx, g_total, *_):
+        L, tensors = ctx.L, ctx.saved_tensors
+        feats, target, weights = tensors[:L], tensors[L:2 * L], tensors[2 * L:]
+        gl = g_total.contiguous()
+        grads = []
+        for f, t, w in zip(feats, target, weights):
+            N, C, h, w_ = f.shape
+            P = h * w_
+            d0 = torch.empty_like(f)
+            lib.vst_lpips_head_bwd(ptr(f), C * P, ptr(t), C * P, ptr(w), ptr(gl), N, C, P, ptr(d0), C * P, None, 0,
+                                   stream())
+            grads.append(d0)
+        return (None, *grads, *([None] * (2 * L)))
+
+
+class _MeanFn(torch.autograd.Function):
+    """weight * mean_n total[n] as a 0-d tensor (`vst_lpips_mean` / `vst_lpips_mean_bwd`)."""
+
+    @staticmethod
+    def forward(ctx, total, weight):
+        out = torch.empty((), dtype=torch.float32, device=total.device)
+        lib.vst_lpips_mean(ptr(total), total.numel(), float(weight), ptr(out), stream())
+        ctx.args = (total.numel(), float(weight))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        N, weight = ctx.args
+        gl = torch.empty(N, dtype=torch.float32, device=g.device)
+        lib.vst_lpips_mean_bwd(ptr(g.contiguous()), N, weight, ptr(gl), stream())
+        return gl, None
+
+
+class LPIPSTarget:
+    """The target side of `LPIPS.distance_to`: its five trunk features (no gradient) and N, H, W."""
+
+    def __init__(self, feats, N, H, W):
+        self.feats, self.N, self.H, self.W = tuple(feats), N, H, W
+
 
 class LPIPS(nn.Module):
     """AA/lpips/lpips.py:24-161 for net="vgg" / "vgg16"."""
@@ -214,16 +327,17 @@ class LPIPS(nn.Module):
             self.eval()
 
     # -- inputs ----------------------------------------------------------------------------------
-    def _batch(self, N, H, W, like):
+    def _batch(self, N, H, W, like, sides=2):
         if H < MIN_SIDE or W < MIN_SIDE:
             raise VstError(f"lpips: images must be at least {MIN_SIDE} x {MIN_SIDE} (four 2x2 pools), got {H} x {W}")
-        return torch.empty((2 * N, 3, H, W), dtype=torch.float32, device=like.device)
+        return torch.empty((sides * N, 3, H, W), dtype=torch.float32, device=like.device)
 
     def forward(self, in0, in1, retPerLayer=False, normalize=False):
         """in0, in1: (N,3,H,W) fp32 device tensors in [-1,1] (`normalize=True`: in [0,1]).  Returns the
         (N,1,1,1) distances ((N,1,H,W) with spatial=True); retPerLayer: (value, [the five levels])."""
         if in0.requires_grad or in1.requires_grad:
-            raise VstError("lpips: forward only -- inputs that require grad are not carried")
+            raise VstError("lpips: forward only -- inputs that require grad are not carried here; "
+                           "distance_to(encode(in1), in0) is the differentiable entry")
         a, b = ops._check(in0, "in0", 4), ops._check(in1, "in1", 4)
         if a.shape != b.shape or a.shape[1] != 3:
             raise VstError(f"lpips: inputs must be two (N,3,H,W) tensors of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
@@ -247,6 +361,54 @@ class LPIPS(nn.Module):
         for half, t in enumerate((img0_u8, img1_u8)):
             _input(t, x, half * N, N, H, W, True, bgr, False, self.version == "0.1")
         return self._distance(x, N, H, W, retPerLayer)
+
+    # -- the training-loss form: a cached target and a distance differentiable in in0 --------------
+    def _target(self, x, N, H, W):
+        return LPIPSTarget([f.detach() for f in self.net(x)], N, H, W)
+
+    def encode(self, in1, normalize=False):
+        """The target side of `distance_to`, computed once under no_grad: in1 as `forward` takes it.
+        A video trainer encodes the content frame once and reuses it for every prediction."""
+        b = ops._check(in1, "in1", 4)
+        if b.shape[1] != 3:
+            raise VstError(f"lpips: the target must be (N,3,H,W), got {tuple(b.shape)}")
+        N, _, H, W = b.shape
+        x = self._batch(N, H, W, b, sides=1)
+        _input(b.detach(), x, 0, N, H, W, False, False, normalize, self.version == "0.1")
+        return self._target(x, N, H, W)
+
+    def encode_u8(self, frames, bgr=True):
+        """`encode` from (N,H,W,3) uint8 device frames (bgr: cv2's channel order), as `forward_u8`."""
+        if frames.dim() != 4 or frames.shape[-1] != 3:
+            raise VstError(f"lpips: frames must be (N,H,W,3) uint8, got {tuple(frames.shape)}")
+        N, H, W, _ = frames.shape
+        ops._ptr_u8(frames, "frames")
+        x = self._batch(N, H, W, frames, sides=1)
+        _input(frames, x, 0, N, H, W, True, bgr, False, self.version == "0.1")
+        return self._target(x, N, H, W)
+
+    def distance_to(self, target, in0, normalize=False, retPerLayer=False):
+        """The (N,1,1,1) distances of in0 ((N,3,H,W) fp32, in [-1,1]; `normalize=True`: in [0,1]) to an
+        encoded target, differentiable with respect to in0: the input pass and the trunk run over in0's N
+        images only, the five fused heads and their fused backward (`vst_lpips_head_bwd`) carry the
+        gradient into the trunk's data gradients.  Per-layer values (retPerLayer) are detached.  Nothing
+        is recorded when in0 does not require grad or grad mode is off."""
+        if self.spatial:
+            raise VstError("lpips: distance_to carries no per-pixel map (spatial=True); use forward")
+        if not isinstance(target, LPIPSTarget):
+            raise VstError("lpips: distance_to needs the LPIPSTarget of encode() / encode_u8()")
+        a = ops._check(in0, "in0", 4)
+        if tuple(a.shape) != (target.N, 3, target.H, target.W):
+            raise VstError(f"lpips: in0 {tuple(a.shape)} does not match the target's "
+                           f"{(target.N, 3, target.H, target.W)}")
+        N = target.N
+        # normalize: 2 is PerceptualLoss's [0,255] form (the 1/255 folded into the input pass)
+        x = _InputFn.apply(a, int(normalize), self.version == "0.1")
+        feats = self.net.forward_grad(x)
+        weights = [self.lins[k].weight.detach().reshape(-1) if self.lpips else None for k in range(self.L)]
+        total, *layers = _HeadsFn.apply(self.L, *feats, *target.feats, *weights)
+        val = total.view(N, 1, 1, 1)
+        return (val, [v.view(N, 1, 1, 1) for v in layers]) if retPerLayer else val
 
     # -- trunk + heads ---------------------------------------------------------------------------
     def _distance(self, x, N, H, W, retPerLayer):
@@ -274,3 +436,29 @@ class LPIPS(nn.Module):
             val = total.view(N, 1, 1, 1)
             res = [v.view(N, 1, 1, 1) for v in layers]
         return (val, res) if retPerLayer else val
+
+
+class PerceptualLoss(nn.Module):
+    """LPIPS as a training-loss term over what the trainers hold: fp32 RGB planes in [0,255].
+    `set_target(frames255)` encodes the target once (a video trainer's content frame);
+    `forward(pred255)` returns `weight * mean_n distance` as a 0-d tensor, differentiable in pred255,
+    which composes with `ops.sum_scalars`.  The 1/255 scaling and its backward are part of the input
+    pass (`vst_lpips_input` / `vst_lpips_input_bwd`, normalize = 2)."""
+
+    def __init__(self, model, weight=1.0):
+        super().__init__()
+        if not isinstance(model, LPIPS):
+            raise VstError("PerceptualLoss: model must be a vst.lpips.LPIPS")
+        self.model = model
+        self.weight = float(weight)
+        self.target = None
+
+    def set_target(self, frames255):
+        self.target = self.model.encode(frames255, normalize=2)
+        return self
+
+    def forward(self, pred255):
+        if self.target is None:
+            raise VstError("PerceptualLoss: set_target(frames255) first")
+        total = self.model.distance_to(self.target, pred255, normalize=2).view(-1)
+        return _MeanFn.apply(total, self.weight)
