@@ -132,7 +132,9 @@ int vst_fold_border(const float* border, const float* mask, float* dx, long NC, 
  * AA/network.py:99), in exact fp32 on the VALU: dx = [mask > 0] * (the interior of the transposed conv
  * of dy over the padded grid); reflect != 0 adds the padded grid's ring through `border`
  * ([N][Cin][H+2][W+2], only its ring is written) and vst_fold_border.  w: [Cout][Cin][3][3];
- * Cin even, W % 4 == 0, W >= 8; mask NULL or dx-shaped. */
+ * mask NULL or dx-shaped.  vst_conv_dgrad_thin_ok: 1 where the entry takes the geometry, else 0 (the
+ * entry's own argument check; pure host arithmetic). */
+long vst_conv_dgrad_thin_ok(int Cout, int Cin, int H, int W);
 int vst_conv_dgrad_thin(const float* dy, const float* w, const float* mask, float* dx, float* border, int N, int Cout,
                         int Cin, int H, int W, int reflect, void* stream);
 /* forward of the same conv (3x3 stride 1 pad 1, reflect != 0: reflection pad, else zero pad; 1..4 output
@@ -228,17 +230,29 @@ int vst_fold_ring(const float* ring, float* dx, long NC, int Hs, int Ws, int KS,
 /* adjoint of (nearest x`up` upsample -> ReflectionPad2d(pad)): dpad [NC][Hs*up+2p][Ws*up+2p] -> dx [NC][Hs][Ws] */
 int vst_fold_reflect(const float* dpad, float* dx, long NC, int Hs, int Ws, int pad, int up, int accumulate,
                      void* stream);
-/* weight gradient, split-K over output pixels with deterministic slab reduction;
+/* weight gradient, split-K over output pixels with deterministic slab reduction, on one of three kernels:
+ *   VST_WGRAD_ROWTILED  the row-tiled GEMM: every geometry and mode;
+ *   VST_WGRAD_HALO      3x3 stride-1 pad-1 convs (ResidualBlock, the AdaAttN decoder) under the
+ *                       split-product modes: one block owns all nine taps of a channel block and walks a
+ *                       column strip down the rows, the source rows in an LDS ring (each loaded and split
+ *                       once instead of nine times); same sums, other fp32 summation order;
+ *   VST_WGRAD_THIN      3x3 stride-1 pad-1 convs with at most 4 output channels (the AdaAttN decoder's
+ *                       last conv, 64 -> 3): a VALU kernel in exact fp32 whatever the mode (each source row
+ *                       loaded once, deterministic slab sums).
+ * The library picks, thin before halo before row-tiled, each where its channel / width / height rules
+ * admit the geometry; VST_GEMM_PERTAP in `mode` selects the row-tiled kernel.  vst_conv_wgrad_kernel
+ * answers which one vst_conv_wgrad runs for a geometry and mode when given the workspace
+ * vst_conv_wgrad_workspace names, or -1 for arguments vst_conv_wgrad refuses (pure host arithmetic; the
+ * choice does not depend on N): callers ask it and do not re-derive the rules.
  * workspace / ws_floats: at least vst_conv_wgrad_workspace(same geometry and mode) floats.  A workspace
- * smaller than that but at least vst_wgrad_workspace(N, Cout, KH*KW*Cin, Ho*Wo) (the row-tiled kernel's
- * need) runs the row-tiled kernel; a smaller one returns VST_EINVAL.  3x3 stride-1 pad-1 convs over
- * 32-channel multiples with 16-multiple widths (ResidualBlock, the AdaAttN decoder) run on the halo
- * weight gradient under the split-product modes (bf16x6 / bf16 / fp16): one block owns all nine taps
- * of 32 input channels and walks a 16-column strip down the rows, the source rows in an LDS ring (each
- * loaded and split once instead of nine times).  VST_GEMM_PERTAP in `mode` selects the row-tiled
- * kernel instead (same sums, other fp32 summation order).  Cout <= 4 (the AdaAttN decoder's last conv,
- * 64 -> 3) with 3x3 stride-1 pad-1, Cin % 4 == 0, Ws % 4 == 0: a VALU kernel in exact fp32 whatever the
- * mode (each source row loaded once, deterministic slab sums; PERTAP selects the GEMM here too). */
+ * smaller than the chosen kernel's need runs the next kernel of that order it is large enough for: one of
+ * at least vst_wgrad_workspace(N, Cout, KH*KW*Cin, Ho*Wo) (the row-tiled kernel's need) always runs; a
+ * smaller one returns VST_EINVAL. */
+#define VST_WGRAD_ROWTILED 0
+#define VST_WGRAD_HALO 1
+#define VST_WGRAD_THIN 2
+long vst_conv_wgrad_kernel(int Cin, int Hs, int Ws, int Cout, int Ho, int Wo, int KH, int KW, int gmode, int stride,
+                           int pad, int up, int mode);
 long vst_wgrad_workspace(int N, int M, int J, int HWo);
 long vst_conv_wgrad_workspace(int N, int Cin, int Hs, int Ws, int Cout, int Ho, int Wo, int KH, int KW, int gmode,
                               int stride, int pad, int up, int mode);

@@ -71,6 +71,57 @@ def test_host_side_argument_validation_without_gpu():
     assert lib.vst_conv_wgrad(1, 1, 1, 1, small, n, cin, h, w, cout, ho, wo, kh, kw, gm, st, pd, up, 0, 3, None) == -1
 
 
+def test_header_constants():
+    """The `#define VST_<NAME> <integer>` reader: the header's values, which vst.ops builds its own from."""
+    c = _lib.parse_constants()
+    assert c == {"GEMM_F32": 0, "GEMM_BF16X3": 1, "GEMM_BF16": 2, "GEMM_BF16X6": 3, "GEMM_F16": 4, "GEMM_KBLOCK": 16,
+                 "GEMM_PERTAP": 32, "GEMM_NOSPLIT": 64, "INSTNORM_MAX_CHUNKS": 256, "SCALER_WS": 1024,
+                 "FRAME_MSE_WS_BYTES": 16384, "RAGGED_DESC_INTS": 16,
+                 "WGRAD_ROWTILED": 0, "WGRAD_HALO": 1, "WGRAD_THIN": 2}
+    from vst import ops
+
+    assert ops.GEMM_MODES == {"f32": 0, "bf16x3": 1, "bf16": 2, "bf16x6": 3, "f16": 4}
+    assert (ops.KBLOCK, ops.PERTAP, ops.IN_MAX_CHUNKS, ops.FRAME_MSE_WS_BYTES, ops.RAGGED_DESC_INTS) == \
+        (16, 32, 256, 16384, 16)
+
+
+@pytest.mark.skipif(not os.path.exists(_lib.LIB_PATH), reason="libvst_hip.so not built")
+def test_wgrad_kernel_and_thin_dgrad_queries():
+    """vst_conv_wgrad_kernel at the boundaries of the thin and halo predicates (pure host calls), the
+    row-tiled kernel's workspace wherever it answers ROWTILED, and vst_conv_dgrad_thin_ok."""
+    lib = _lib.lib.load()
+    ROWTILED, HALO, THIN = 0, 1, 2
+    F32, BF16X6, F16, PERTAP = 0, 3, 4, 32
+    # (Cin, H, W, Cout, stride, mode) of a 3x3 pad-1 conv -> kind
+    cases = [
+        # at most 4 outputs: 4-channel groups, 4-column quads from 8 columns up, two rows, stride 1
+        ((64, 2, 8, 3, 1, F32), THIN), ((64, 2, 12, 3, 1, F32), THIN), ((64, 1, 8, 3, 1, F32), ROWTILED),
+        ((64, 2, 10, 3, 1, F32), ROWTILED), ((6, 2, 8, 3, 1, F32), ROWTILED), ((64, 2, 8, 3, 2, F32), ROWTILED),
+        # 64-row tiles: 32-channel blocks and 32-column strips under a split-product mode
+        ((32, 2, 32, 64, 1, BF16X6), HALO), ((32, 2, 16, 64, 1, BF16X6), ROWTILED), ((32, 2, 32, 64, 1, F32), ROWTILED),
+        ((48, 2, 32, 64, 1, BF16X6), ROWTILED),
+        # 128-row tiles under a single-product mode: 64-column strips
+        ((32, 2, 64, 128, 1, F16), HALO), ((32, 2, 32, 128, 1, F16), ROWTILED),
+    ]
+    for (Cin, H, W, Cout, stride, mode), kind in cases:
+        Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
+        geom = (Cin, H, W, Cout, Ho, Wo, 3, 3, 1, stride, 1, 1)
+        assert lib.vst_conv_wgrad_kernel(*geom, mode) == kind, (geom, mode)
+        assert lib.vst_conv_wgrad_kernel(*geom, mode | PERTAP) == ROWTILED, (geom, mode)
+        for m in (mode | PERTAP,) + ((mode,) if kind == ROWTILED else ()):
+            for N in (1, 2):
+                assert lib.vst_conv_wgrad_workspace(N, *geom, m) == lib.vst_wgrad_workspace(N, Cout, 9 * Cin, Ho * Wo)
+    ok = (64, 2, 8, 3, 2, 8, 3, 3, 1, 1, 1, 1)
+    for bad in (-1, 5, 7, 8):
+        assert lib.vst_conv_wgrad_kernel(*ok, bad) == -1
+    for i in (0, 3, 4, 5, 6, 7):  # Cin, Cout, Ho, Wo, KH, KW
+        for v in (0, -1):
+            assert lib.vst_conv_wgrad_kernel(*ok[:i], v, *ok[i + 1:], F32) == -1, (i, v)
+    assert lib.vst_conv_dgrad_thin_ok(3, 16, 2, 8) == 1
+    for geom in ((3, 16, 1, 8), (3, 16, 2, 4), (3, 16, 2, 10), (3, 3, 2, 8), (5, 16, 2, 8)):
+        assert lib.vst_conv_dgrad_thin_ok(*geom) == 0, geom
+
+
 @pytest.mark.skipif(not os.path.exists(_lib.LIB_PATH), reason="libvst_hip.so not built")
 def test_build_provenance_matches_tree():
     """vst_build_id() (baked in by csrc/Makefile) equals the hash of this tree's csrc + header."""

@@ -109,7 +109,8 @@ def routes(layer):
     with ops.policy_scope(scope):
         dgrad, nws = ops.conv_dgrad_route(N, Cin, Cout, H, W, Ho, Wo, ks, (ks, ks), stride, pad, pad_mode, up, masked,
                                           ops.gemm_role("dgrad"))
-        wgrad, flags, family = ops.conv_wgrad_route(Cin, Cout, W, ks, stride, pad, pad_mode, up, ops.gemm_role("wgrad"))
+        wgrad, flags, family = ops.conv_wgrad_route(Cin, Cout, W, ks, stride, pad, pad_mode, up, ops.gemm_role("wgrad"),
+                                                    H=H)
     assert (nws >= 0) if dgrad == "reflect3" else nws == 0
     assert flags in (0, ops.PERTAP) and (wgrad == "gemm" or flags == 0)
     assert family is None if wgrad == "rowsplit" else family in ("wgrad", "thin")
@@ -167,6 +168,11 @@ def test_routes_outside_the_benchmark_layers():
         ops.conv_dgrad_route(1, 16, 16, 8, 16, 16, 32, 3, (3, 3), 1, 1, "zero", 2, False, m)
     # a zero-pad thin-output conv: no row-split form, so VST_THIN_WGRAD=0 puts it on the row-tiled GEMM
     assert ops.conv_wgrad_route(64, 3, 64, 3, 1, 1, "zero", 1, m) == ("gemm", 0, "thin")
+    # a one-row plane: the library's VALU kernels need two rows, and the routes follow its answer
+    assert ops.conv_dgrad_route(1, 16, 3, 1, 16, 1, 16, 3, (3, 3), 1, 1, "zero", 1, False, m) == ("zero", 0)
+    assert ops.conv_wgrad_route(16, 3, 16, 3, 1, 1, "zero", 1, m, H=1) == ("gemm", 0, "wgrad")
+    assert ops.conv_dgrad_route(1, 16, 3, 2, 16, 2, 16, 3, (3, 3), 1, 1, "zero", 1, False, m) == ("thin", 0)
+    assert ops.conv_wgrad_route(16, 3, 16, 3, 1, 1, "zero", 1, m, H=2) == ("gemm", 0, "thin")
 
 
 # switch, its default, the layer it routes, the policy, which of the three routes, default-state and

@@ -147,6 +147,22 @@ def test_thin_wgrad_vs_fp64(shape, gmode, mode):
     assert float((rowt.double() - ref).abs().max()) / scale < TOL[mode]
 
 
+def test_one_row_plane_runs_rowtiled():
+    """A one-row plane with <= 4 outputs: the VALU kernel needs two rows, so vst_conv_wgrad runs the
+    row-tiled GEMM, as vst_conv_wgrad_kernel says -- bitwise the VST_GEMM_PERTAP result."""
+    N, Cin, H, W, Cout = 1, 16, 1, 16, 3
+    mode = BF16X6
+    assert lib.vst_conv_wgrad_kernel(Cin, H, W, Cout, H, W, 3, 3, 1, 1, 1, 1, mode) == 0  # VST_WGRAD_ROWTILED
+    x = _rand(N, Cin, H, W, seed=16, scale=2.0)
+    dy = _rand(N, Cout, H, W, seed=17, scale=0.5)
+    dw = _wgrad(dy, x, Cout, 1, mode)
+    rowt = _wgrad(dy, x, Cout, 1, mode | PERTAP)
+    torch.cuda.synchronize()
+    assert torch.equal(dw, rowt)
+    ref = _ref(dy, x, 1)
+    assert float((dw.double() - ref).abs().max()) / float(ref.abs().max()) < TOL[mode]
+
+
 def test_thin_wgrad_accumulate_deterministic_and_workspace():
     N, Cin, H, W, Cout = 2, 64, 24, 64, 3
     x = _rand(N, Cin, H, W, seed=13)

@@ -658,12 +658,18 @@ int vst_thin_wgrad_launch(const float* dy, const float* x, float* dw, float* sla
   return thin_wgrad_launch_impl(dy, x, dw, slab, N, Cin, H, W, Cout, gmode, accumulate, st);
 }
 
+// the thin data gradient's geometry: 1..4 output channels, channel pairs, 4-column quads, two rows
+static bool thin_dgrad_ok(int Cout, int Cin, int H, int W) {
+  return Cout >= 1 && Cout <= 4 && Cin > 0 && Cin % THIN_DG_CI == 0 && H >= 2 && W >= 8 && W % 4 == 0;
+}
+
 extern "C" {
+
+long vst_conv_dgrad_thin_ok(int Cout, int Cin, int H, int W) { return thin_dgrad_ok(Cout, Cin, H, W); }
 
 int vst_conv_dgrad_thin(const float* dy, const float* w, const float* mask, float* dx, float* border, int N, int Cout,
                         int Cin, int H, int W, int reflect, void* stream) {
-  VST_CHECK_ARG(dy && w && dx && N > 0 && Cout >= 1 && Cout <= 4 && Cin > 0 && Cin % THIN_DG_CI == 0 && H >= 2 &&
-                W >= 8 && W % 4 == 0 && (!reflect || border));
+  VST_CHECK_ARG(dy && w && dx && N > 0 && thin_dgrad_ok(Cout, Cin, H, W) && (!reflect || border));
   hipStream_t st = (hipStream_t)stream;
   // a row lane covers up to 256 column quads; row chunks until ~2048 blocks (>= 4 rows per lane)
   const int quads = W / 4;

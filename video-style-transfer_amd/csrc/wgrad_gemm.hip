@@ -8,6 +8,7 @@
 // pixels r of ONE image per block (grid.z = N * S splits); partial slabs are summed by
 // `wgrad_reduce` (into PyTorch's [co][ci][kh][kw] order) or `gram_reduce` (per image, scaled),
 // which keeps the result deterministic (no float atomics).
+#include <climits>
 #include <cstdlib>
 
 #include <type_traits>
@@ -1174,59 +1175,84 @@ int vst_conv_wgrad_up2(const float* dy, const float* x, float* dw, float* worksp
 // workspace (floats) needed by vst_conv_wgrad / vst_conv_wgrad_rowsplit / vst_gram
 long vst_wgrad_workspace(int N, int M, int J, int HWo) { return wg_plan(N, M, J, HWo).floats(N); }
 
-// the halo weight gradient (wgrad_halo.hip) applies: 3x3 stride-1 pad-1 over 32-channel blocks and
-// 16-column strips, a split-product mode, unless the call asks for the row-tiled kernel
-static bool use_wgrad_halo(int Cout, const WgGather& g, int mode) {
-  return !(mode & VST_GEMM_PERTAP) && g.Ho == g.Hs && g.Wo == g.Ws &&
-         wgrad_halo_ok(Cout, g.Cs, g.Hs, g.Ws, g.KH, g.KW, g.stride, g.pad, g.up, g.gmode, mode);
+// the geometry and mode vst_conv_wgrad takes (its pointers and batch size apart)
+static bool conv_wgrad_args_ok(int Cin, int Cout, int Ho, int Wo, int KH, int KW, int gmode, int stride, int up,
+                               int mode) {
+  return vst_mode_ok(mode) && Cin > 0 && Cout > 0 && Ho > 0 && Wo > 0 && KH > 0 && KW > 0 &&
+         (gmode == 0 || gmode == 1) && (stride == 1 || stride == 2) && (up == 1 || up == 2);
+}
+
+// The kernel vst_conv_wgrad runs for one geometry and mode, with what its launch needs.
+struct WgChoice {
+  int kind;     // VST_WGRAD_*
+  WgGather g;
+  WgPlan p;     // the row-tiled plan
+  WhPlan hp;    // the halo plan (kind == VST_WGRAD_HALO)
+  long floats;  // workspace floats of the chosen kernel
+};
+// The one walk: the fp32 VALU kernel (at most 4 output channels; exact fp32 whatever the mode's MFMA
+// arithmetic), else the halo kernel, else the row-tiled GEMM -- each of the first two only where its
+// workspace fits ws_cap, so a workspace sized for the row-tiled kernel (the pre-halo rule) runs row-tiled.
+static WgChoice wg_choose(int N, int Cin, int Hs, int Ws, int Cout, int Ho, int Wo, int KH, int KW, int gmode,
+                          int stride, int pad, int up, int mode, long ws_cap) {
+  WgChoice c;
+  c.g.Cs = Cin, c.g.Hs = Hs, c.g.Ws = Ws, c.g.Ho = Ho, c.g.Wo = Wo;
+  c.g.KH = KH, c.g.KW = KW, c.g.gmode = gmode, c.g.stride = stride, c.g.pad = pad, c.g.up = up;
+  c.p = wg_plan(N, Cout, c.g);
+  c.hp = WhPlan{};
+  if (vst_thin_wgrad_ok(Cout, Cin, Hs, Ws, Ho, Wo, KH, KW, gmode, stride, pad, up, mode) &&
+      (c.floats = vst_thin_wgrad_floats(N, Cout, Cin, Hs, Ws)) <= ws_cap) {
+    c.kind = VST_WGRAD_THIN;
+    return c;
+  }
+  // (the halo kernel, wgrad_halo.hip, unless the call asks for the row-tiled one)
+  if (!(mode & VST_GEMM_PERTAP) && Ho == Hs && Wo == Ws &&
+      wgrad_halo_ok(Cout, Cin, Hs, Ws, KH, KW, stride, pad, up, gmode, mode)) {
+    c.hp = wgrad_halo_plan(N, Cout, Cin, Hs, Ws, mode);
+    if ((c.floats = wgrad_halo_slab_floats(Cin, c.hp)) <= ws_cap) {
+      c.kind = VST_WGRAD_HALO;
+      return c;
+    }
+  }
+  c.kind = VST_WGRAD_ROWTILED;
+  c.floats = c.p.floats(N);
+  return c;
+}
+
+long vst_conv_wgrad_kernel(int Cin, int Hs, int Ws, int Cout, int Ho, int Wo, int KH, int KW, int gmode, int stride,
+                           int pad, int up, int mode) {
+  if (!conv_wgrad_args_ok(Cin, Cout, Ho, Wo, KH, KW, gmode, stride, up, mode)) return -1;
+  return wg_choose(1, Cin, Hs, Ws, Cout, Ho, Wo, KH, KW, gmode, stride, pad, up, mode, LONG_MAX).kind;
 }
 
 long vst_conv_wgrad_workspace(int N, int Cin, int Hs, int Ws, int Cout, int Ho, int Wo, int KH, int KW, int gmode,
                               int stride, int pad, int up, int mode) {
   if (N <= 0 || Cin <= 0 || Cout <= 0 || Ho <= 0 || Wo <= 0 || KH <= 0 || KW <= 0 || !vst_mode_ok(mode)) return 0;
-  if (vst_thin_wgrad_ok(Cout, Cin, Hs, Ws, Ho, Wo, KH, KW, gmode, stride, pad, up, mode))
-    return vst_thin_wgrad_floats(N, Cout, Cin, Hs, Ws);
-  WgGather g;
-  g.Cs = Cin, g.Hs = Hs, g.Ws = Ws, g.Ho = Ho, g.Wo = Wo;
-  g.KH = KH, g.KW = KW, g.gmode = gmode, g.stride = stride, g.pad = pad, g.up = up;
-  if (use_wgrad_halo(Cout, g, mode)) return wgrad_halo_slab_floats(Cin, wgrad_halo_plan(N, Cout, Cin, Hs, Ws, mode));
-  return wg_plan(N, Cout, g).floats(N);
+  return wg_choose(N, Cin, Hs, Ws, Cout, Ho, Wo, KH, KW, gmode, stride, pad, up, mode, LONG_MAX).floats;
 }
 
 int vst_conv_wgrad(const float* dy, const float* x, float* dw, float* workspace, long ws_floats, int N, int Cin,
                    int Hs, int Ws, int Cout, int Ho, int Wo, int KH, int KW, int gmode, int stride, int pad, int up,
                    int accumulate, int mode, void* stream) {
-  VST_CHECK_ARG(vst_mode_ok(mode));
-  VST_CHECK_ARG(dy && x && dw && workspace && N > 0 && Cin > 0 && Cout > 0 && Ho > 0 && Wo > 0 && KH > 0 && KW > 0);
-  VST_CHECK_ARG((gmode == 0 || gmode == 1) && (stride == 1 || stride == 2) && (up == 1 || up == 2));
+  VST_CHECK_ARG(dy && x && dw && workspace && N > 0);
+  VST_CHECK_ARG(conv_wgrad_args_ok(Cin, Cout, Ho, Wo, KH, KW, gmode, stride, up, mode));
   hipStream_t st = (hipStream_t)stream;
-  // at most 4 output channels: the VALU kernel (exact fp32, whatever the mode's MFMA arithmetic),
-  // given the workspace vst_conv_wgrad_workspace names for it
-  if (vst_thin_wgrad_ok(Cout, Cin, Hs, Ws, Ho, Wo, KH, KW, gmode, stride, pad, up, mode) &&
-      ws_floats >= vst_thin_wgrad_floats(N, Cout, Cin, Hs, Ws))
+  const WgChoice c = wg_choose(N, Cin, Hs, Ws, Cout, Ho, Wo, KH, KW, gmode, stride, pad, up, mode, ws_floats);
+  VST_CHECK_ARG(ws_floats >= c.floats);  // (smaller than the row-tiled kernel's need: refused)
+  if (c.kind == VST_WGRAD_THIN)
     return vst_thin_wgrad_launch(dy, x, dw, workspace, N, Cin, Hs, Ws, Cout, gmode, accumulate, st);
-  WgGather g;
-  g.Cs = Cin, g.Hs = Hs, g.Ws = Ws, g.Ho = Ho, g.Wo = Wo;
-  g.KH = KH, g.KW = KW, g.gmode = gmode, g.stride = stride, g.pad = pad, g.up = up;
-  const WgPlan p = wg_plan(N, Cout, g);
-  bool halo = use_wgrad_halo(Cout, g, mode);
-  const WhPlan hp = halo ? wgrad_halo_plan(N, Cout, Cin, Hs, Ws, mode) : WhPlan{};
-  // a workspace sized for the row-tiled kernel (the pre-halo rule) but smaller than the halo slabs
-  // runs row-tiled; one smaller than both is refused
-  if (halo && ws_floats < wgrad_halo_slab_floats(Cin, hp)) halo = false;
-  VST_CHECK_ARG(halo || ws_floats >= p.floats(N));
-  const long total = (long)Cout * p.J;
-  if (halo) {
-    int rc = wgrad_halo_launch(hp, dy, x, workspace, N, Cout, Cin, Hs, Ws, gmode, mode, st);
+  const long total = (long)Cout * c.p.J;
+  if (c.kind == VST_WGRAD_HALO) {
+    int rc = wgrad_halo_launch(c.hp, dy, x, workspace, N, Cout, Cin, Hs, Ws, gmode, mode, st);
     if (rc) return rc;
-    wgrad_reduce_kernel<<<ceil_div(total, 256), 256, 0, st>>>(workspace, dw, hp.NB, Cout, hp.Mpad, 9 * Cin, Cin, 3, 3,
-                                                             0, 1.0f, accumulate);
+    wgrad_reduce_kernel<<<ceil_div(total, 256), 256, 0, st>>>(workspace, dw, c.hp.NB, Cout, c.hp.Mpad, 9 * Cin, Cin, 3,
+                                                             3, 0, 1.0f, accumulate);
     return vst_launch_status();
   }
-  int rc = run_wg(p, g, dy, x, workspace, N, mode, st);
+  int rc = run_wg(c.p, c.g, dy, x, workspace, N, mode, st);
   if (rc) return rc;
-  wgrad_reduce_kernel<<<ceil_div(total, 256), 256, 0, st>>>(workspace, dw, N * p.S, Cout, p.Mpad, p.Jpad, Cin, KH, KW, 0,
-                                                           1.0f, accumulate);
+  wgrad_reduce_kernel<<<ceil_div(total, 256), 256, 0, st>>>(workspace, dw, N * c.p.S, Cout, c.p.Mpad, c.p.Jpad, Cin, KH,
+                                                           KW, 0, 1.0f, accumulate);
   return vst_launch_status();
 }
 

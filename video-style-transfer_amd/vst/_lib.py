@@ -71,6 +71,15 @@ def parse_header(path=HEADER_PATH):
     return protos
 
 
+def parse_constants(path=HEADER_PATH):
+    """{NAME: value} for every `#define VST_<NAME> <integer>` in the header."""
+    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    return {m.group(1): int(m.group(2)) for m in re.finditer(r"^\s*#\s*define\s+VST_(\w+)\s+(-?\d+)\s*$", text, flags=re.M)}
+
+
+CONSTANTS = parse_constants()
+
+
 class VstError(RuntimeError):
     pass
 

@@ -13,7 +13,7 @@ import torch
 from torch.autograd import Function
 
 from . import kprof
-from ._lib import VstError, lib, ptr, ptr_rows, stream
+from ._lib import CONSTANTS as _C, VstError, lib, ptr, ptr_rows, stream
 
 GM_REFLECT, GM_ZERO, GM_TRANSPOSED = 0, 1, 2
 EPI_BIAS, EPI_RELU, EPI_TANH, EPI_MASK, EPI_ACCUM = 1, 2, 4, 8, 16
@@ -36,9 +36,12 @@ def _check(t, name, ndim=None):
     return t.contiguous()
 
 
-GEMM_MODES = {"f32": 0, "bf16x3": 1, "bf16": 2, "bf16x6": 3, "f16": 4}
-KBLOCK = 16  # VST_GEMM_KBLOCK: channel-blocked K order flag of a conv pack + GEMM call pair
-PERTAP = 32  # VST_GEMM_PERTAP: the per-tap conv / row-tiled weight-gradient kernel for this call
+# (the values of include/vst_hip.h's #defines are read from the header, like the prototypes)
+GEMM_MODES = {name: _C["GEMM_" + name.upper()] for name in ("f32", "bf16x3", "bf16", "bf16x6", "f16")}
+KBLOCK = _C["GEMM_KBLOCK"]  # channel-blocked K order flag of a conv pack + GEMM call pair
+PERTAP = _C["GEMM_PERTAP"]  # the per-tap conv / row-tiled weight-gradient kernel for this call
+# the kernel vst_conv_wgrad runs (vst_conv_wgrad_kernel's answer)
+WGRAD_ROWTILED, WGRAD_HALO, WGRAD_THIN = _C["WGRAD_ROWTILED"], _C["WGRAD_HALO"], _C["WGRAD_THIN"]
 # where the channel-blocked K order applies (VST_KBLOCK): "res" (default) the loss networks, the
 # ReCoNet stylizer's residual blocks and the AdaAttN decoder (scope "stylizer.dec": no InstanceNorm
 # there, and its 3x3 convs then run on the halo-tiled kernel); "1" nowhere inside a stylizer; "2"
@@ -383,7 +386,7 @@ def conv_dgrad_route(N, Cin, Cout, H, W, Ho, Wo, ks, wk, stride, pad, pad_mode, 
     if (pad_mode == "zero" and up == 1 and stride == 1 and not masked and Cin % 16 != 0 and Cin * ks * ks <= 32
             and (H, W) == (Ho, Wo)):
         return "tapsum", 0  # few input channels (VGG conv1_1)
-    if thin_dgrad_ok(Cout, Cin, ks, stride, pad, up, W):
+    if thin_dgrad_ok(Cout, Cin, ks, stride, pad, up, H, W):
         return "thin", 0
     if pad_mode == "zero" and up == 1:
         return "zero", 0
@@ -459,9 +462,18 @@ def conv_dgrad_fold(gz, w, x_shape, geom, flops, mode, dmask=None, nws=0):
 THIN_DGRAD = os.environ.get("VST_THIN_DGRAD", "1") != "0"  # A/B: Cout <= 4 3x3 data gradients on the VALU kernel
 
 
-def thin_dgrad_ok(Cout, Cin, ks, stride, pad, up, W):
-    return THIN_DGRAD and Cout <= 4 and ks == 3 and stride == 1 and pad == 1 and up == 1 and Cin % 2 == 0 \
-        and W % 4 == 0 and W >= 8
+_THIN_DGRAD_OK = {}  # (Cout, Cin, H, W) -> vst_conv_dgrad_thin_ok (host arithmetic)
+
+
+def thin_dgrad_ok(Cout, Cin, ks, stride, pad, up, H, W):
+    """A 3x3 stride-1 pad-1 conv whose geometry vst_conv_dgrad_thin takes (the library's answer)."""
+    if not (THIN_DGRAD and ks == 3 and stride == 1 and pad == 1 and up == 1):
+        return False
+    key = (Cout, Cin, H, W)
+    ok = _THIN_DGRAD_OK.get(key)
+    if ok is None:
+        ok = _THIN_DGRAD_OK[key] = bool(lib.vst_conv_dgrad_thin_ok(*key))
+    return ok
 
 
 def conv_dgrad_thin(gz, w, x_shape, geom, flops, mode, dmask=None, nws=0):
@@ -662,43 +674,58 @@ def rowsplit_ok(Cout, ks, stride, pad_mode, up):
     return Cout * ks <= 32 and ks > 1 and stride == 1 and pad_mode == "reflect" and up == 1
 
 
-def conv_wgrad_route(Cin, Cout, W, ks, stride, pad, pad_mode, up, mode):
-    """(route, flags, profiler family) of the weight gradient of one conv, from the geometry, the mode
-    and this module's A/B switches alone: "up2" (the phase-stacked nearest-x2 form), "rowsplit", or
-    "gemm" (vst_conv_wgrad) with the flags or-ed into its mode (PERTAP: the row-tiled kernel) and the
-    family its launch records ("thin" where the library takes its fp32 VALU kernel)."""
+_WGRAD_KERNEL = {}  # (geometry, mode) -> vst_conv_wgrad_kernel (host arithmetic)
+
+
+def conv_wgrad_kernel(Cin, Cout, H, W, ks, stride, pad, pad_mode, up, mode):
+    """The kernel vst_conv_wgrad runs for this conv in `mode` (WGRAD_ROWTILED / WGRAD_HALO / WGRAD_THIN; -1:
+    it refuses the geometry): the library's answer, never re-derived here."""
+    key = (Cin, Cout, H, W, ks, stride, pad, pad_mode, up, mode)
+    kind = _WGRAD_KERNEL.get(key)
+    if kind is None:
+        Ho, Wo = conv_out_hw(H, W, ks, stride, pad, up)
+        kind = _WGRAD_KERNEL[key] = int(lib.vst_conv_wgrad_kernel(
+            Cin, H, W, Cout, Ho, Wo, ks, ks, GM_REFLECT if pad_mode == "reflect" else GM_ZERO, stride, pad, up, mode))
+    return kind
+
+
+def conv_wgrad_route(Cin, Cout, W, ks, stride, pad, pad_mode, up, mode, H=None):
+    """(route, flags, profiler family) of the weight gradient of one conv, from the geometry, the mode,
+    this module's A/B switches and the library's kernel choice alone: "up2" (the phase-stacked nearest-x2
+    form), "rowsplit", or "gemm" (vst_conv_wgrad) with the flags or-ed into its mode (PERTAP: the
+    row-tiled kernel) and the family its launch records ("thin" exactly where the library runs its fp32
+    VALU kernel).  H: the plane's height, which the library's choice depends on; a caller that leaves it
+    out (the signature before the library was asked) is answered for the square plane, H = W."""
+    H = W if H is None else H
     if _WGRAD_UP2 and up == 2 and ks == 3 and stride == 1 and pad == 1 and pad_mode == "reflect":
         return "up2", 0, "wgrad"
-    # vst_conv_wgrad's own choice (csrc/wgrad_gemm.hip thin_wgrad_ok): its fp32 VALU kernel (the AdaAttN
-    # decoder's last conv, 64 -> 3)
-    thin = THIN_WGRAD and Cout <= 4 and ks == 3 and stride == 1 and up == 1 and Cin % 4 == 0 and W % 4 == 0 and W >= 8
-    # Row-split GEMMs: the tiny-Cout convs (rowsplit_ok), and 64-output 3x3 stride-1 reflect convs over
-    # >= 64 channels (the AdaAttN decoder's conv6 / conv7, AA/network.py:93-96).  Rows (co, kh) read
-    # dY[co][y - kh], columns (kw, ci) read x[ci][y][x + kw]: M = 3 Cout and J = 3 Cin instead of M = Cout
-    # and J = 9 Cin, so each dY tile feeds 3x the rows and is re-read for 3x fewer column tiles
-    # (64 x 576 -> 192 x 192 for 64 -> 64).  Except where the halo weight gradient (vst_conv_wgrad:
-    # 32-channel multiples, split-product modes) beats it (fp16 decoder conv6 1.12 vs 1.41 ms, conv7 3.6 vs
-    # 4.5 ms at config 5, tools/wgrad_bench.py): the row-split form stays for the f32 / bf16x3 modes and
-    # the widths the halo kernel does not take (csrc/wgrad_halo.hip wgrad_halo_ok: its 64-row blocks walk
-    # 32-column strips in every split-product mode, so W % 32 == 0)
-    wide = RS_WGRAD and Cout <= 64 and Cin >= 64 and ks == 3 and stride == 1 and pad_mode == "reflect" and up == 1 \
-        and W % 16 == 0 and not (Cin % 32 == 0 and W % 32 == 0 and (mode & 7) in (
-            GEMM_MODES["bf16x6"], GEMM_MODES["bf16"], GEMM_MODES["f16"]))
-    if not thin and pad == ks // 2 and (rowsplit_ok(Cout, ks, stride, pad_mode, up) or wide):
-        return "rowsplit", 0, None
     flags = 0
     if not WGRAD_HALO_RES and (mode & 7) == GEMM_MODES["bf16x6"] and Cout % 192 == 0 and Cout % 128 != 0:
         flags = PERTAP
     if not THIN_WGRAD and Cout <= 4:
         flags = PERTAP  # (the A/B switch: the row-tiled GEMM instead of the VALU kernel)
-    return "gemm", flags, "thin" if pad == 1 and thin else "wgrad"
+    geom = (Cin, Cout, H, W, ks, stride, pad, pad_mode, up)
+    # vst_conv_wgrad's fp32 VALU kernel (the AdaAttN decoder's last conv, 64 -> 3)
+    thin = conv_wgrad_kernel(*geom, mode | flags) == WGRAD_THIN
+    # Row-split GEMMs: the tiny-Cout convs (rowsplit_ok), and 64-output 3x3 stride-1 reflect convs over
+    # >= 64 channels (the AdaAttN decoder's conv6 / conv7, AA/network.py:93-96).  Rows (co, kh) read
+    # dY[co][y - kh], columns (kw, ci) read x[ci][y][x + kw]: M = 3 Cout and J = 3 Cin instead of M = Cout
+    # and J = 9 Cin, so each dY tile feeds 3x the rows and is re-read for 3x fewer column tiles
+    # (64 x 576 -> 192 x 192 for 64 -> 64).  Except where vst_conv_wgrad runs its halo kernel, which
+    # beats it (fp16 decoder conv6 1.12 vs 1.41 ms, conv7 3.6 vs 4.5 ms at config 5, tools/wgrad_bench.py)
+    wide = RS_WGRAD and Cout <= 64 and Cin >= 64 and ks == 3 and stride == 1 and pad_mode == "reflect" and up == 1 \
+        and W % 16 == 0 and conv_wgrad_kernel(*geom, mode) != WGRAD_HALO
+    if not thin and pad == ks // 2 and (rowsplit_ok(Cout, ks, stride, pad_mode, up) or wide):
+        return "rowsplit", 0, None
+    return "gemm", flags, "thin" if thin else "wgrad"
 
 
 def conv_wgrad(gz, x, w_shape, ks, stride, pad, pad_mode, up, mode=None, out=None):
     """Weight gradient of (upsample x`up` -> pad -> conv(stride)) in `mode` (default: the "wgrad" role's,
     looked up here), accumulated into `out` when given."""
     mode = gemm_role("wgrad") if mode is None else mode
-    route, flags, family = conv_wgrad_route(x.shape[1], w_shape[0], x.shape[3], ks, stride, pad, pad_mode, up, mode)
+    route, flags, family = conv_wgrad_route(x.shape[1], w_shape[0], x.shape[3], ks, stride, pad, pad_mode, up, mode,
+                                            H=x.shape[2])
     if route == "up2":
         return conv_wgrad_up2(gz, x, w_shape, mode, out)
     if route == "rowsplit":
@@ -1762,7 +1789,7 @@ def tensor_to_frames(y, bgr=True, clamped=None, frames=None):
     return frames
 
 
-FRAME_MSE_WS_BYTES = 16384  # VST_FRAME_MSE_WS_BYTES (include/vst_hip.h)
+FRAME_MSE_WS_BYTES = _C["FRAME_MSE_WS_BYTES"]
 
 
 def frame_diff_mse(x0, x1, y0, y1, out):
@@ -1872,7 +1899,7 @@ def tanh_image(v, image=True):
 # ---------------------------------------------------------------- RTNSTV inference (RT/utilities.py:296-332)
 # Forward-only ops of vst.rtnstv.inference: plain functions, no autograd Function.
 IN_SPLIT = os.environ.get("VST_IN_SPLIT", "1") != "0"  # A/B: 0 = the one-workgroup-per-plane kernel everywhere
-IN_MAX_CHUNKS = 256  # VST_INSTNORM_MAX_CHUNKS (include/vst_hip.h)
+IN_MAX_CHUNKS = _C["INSTNORM_MAX_CHUNKS"]
 # Chunks per plane of the split-plane InstanceNorm forward, from (C, HW) alone -- never from N, so a
 # frame's statistics do not depend on the batch it is in.  Set from the measured table of
 # tools/rt_infer_bench.py (profiles/rt_infer_bench.json): planes above IN_SPLIT_MIN_HW
@@ -2097,7 +2124,7 @@ def pil_resize_to_tensor255(images, size, out=None):
 
 
 # ---------------------------------------------------- AdaAttN image datasets: ragged resize-and-crop
-RAGGED_DESC_INTS = 16  # VST_RAGGED_DESC_INTS (include/vst_hip.h)
+RAGGED_DESC_INTS = _C["RAGGED_DESC_INTS"]
 _PIL_HOST_TABLES = {}
 
 
