@@ -338,7 +338,8 @@ def test_pool_warp_gram_losses_bwd():
 @pytest.mark.parametrize("flow", ["random", "converging"])
 def test_warp_bwd_gather(flow):
     """Gather-form warp backward vs the oracle's autograd, with more channels than one channel
-    group and (converging) flows that overflow the per-source tap lists (atomic excess pass)."""
+    group and (converging) flows whose per-source tap lists (up to 240 entries) are too long for the
+    register sorting networks and are sorted by rank in LDS."""
     from vst import ops
 
     g = torch.Generator().manual_seed(21)

@@ -71,8 +71,13 @@ struct Bilin {
   float w[4];  // nw, ne, sw, se
 };
 
-// grid_sample(align_corners=False) bilinear coordinates + weights, same fp32 op order as ATen
+// grid_sample(align_corners=False) bilinear coordinates + weights, same fp32 op order as ATen: every
+// product and sum rounded on its own.  Contracted, (gx + 1) * W - 1 keeps the unrounded product and
+// lands an ulp beside the reference's coordinate -- a sample exactly on a pixel centre then floors to
+// the neighbouring pixel (weights ~1e-7 / ~1 instead of a single-tap copy), and at W ~ 1000 the
+// weights move by 1e-4 (tests/test_gpu_losses.py: the integer-coordinate and 1025 x 1024 warps)
 __device__ __forceinline__ Bilin warp_coords(int x, int y, float u, float v, int H, int W) {
+#pragma clang fp contract(off)
   float gx = 2.0f * ((float)x + u) / (float)max(W - 1, 1) - 1.0f;
   float gy = 2.0f * ((float)y + v) / (float)max(H - 1, 1) - 1.0f;
   float ix = ((gx + 1.f) * W - 1.f) / 2.f;
