@@ -616,6 +616,27 @@ int vst_temporal_error(const float* a, const float* b, const float* flo, const f
 long vst_ssim_workspace(int B, int C, int H, int W);
 int vst_ssim(const float* img1, const float* img2, const float* taps, int win, int B, int C, int H, int W, float* out,
              float* map, void* workspace, int tile, void* stream);
+/* vst_ssim with the two constants as arguments (a data range L other than 1: c1 = (0.01 L)^2, c2 = (0.03 L)^2);
+ * vst_ssim is this entry with (float)(0.01 * 0.01) and (float)(0.03 * 0.03). */
+int vst_ssim_c(const float* img1, const float* img2, const float* taps, int win, int B, int C, int H, int W, float c1,
+               float c2, float* out, float* map, void* workspace, int tile, void* stream);
+/* The backward of vst_ssim_c's scores: gout[b] (device, B floats) is the upstream gradient of out[b]; d1
+ * (and d2 unless NULL) receive dL/dimg1 (dL/dimg2), B x C x H x W.  With w = gout[b] / (C H W), A1 = 2 mu1 mu2
+ * + c1, A2 = 2 (e12 - mu1 mu2) + c2, B1 = mu1^2 + mu2^2 + c1, B2 = (e11 - mu1^2) + (e22 - mu2^2) + c2 and
+ * S = A1 A2 / (B1 B2):
+ *   Dm = 2 mu2 (A2 - A1) / (B1 B2) - 2 mu1 S (1/B1 - 1/B2),  D11 = -S / B2,  D12 = 2 A1 / (B1 B2)
+ *   d1 = w (G*Dm + 2 x (G*D11) + y (G*D12))       (d2: x <-> y, mu1 <-> mu2; D11 and D12 are shared)
+ * with G the zero-padded window and the D maps zero outside the image.  One kernel, one block per 32 x 32
+ * tile of a plane: the tile + 2 R halo of both images staged in LDS, the moments recomputed on the tile + R
+ * halo (the forward saves nothing), the D maps and the second separable pass in LDS, each element written
+ * once by one thread.  No atomics, no workspace: bitwise reproducible, image n of a batch is bitwise the
+ * image alone, and d1 does not depend on whether d2 is wanted.  Limits as vst_ssim. */
+int vst_ssim_bwd(const float* img1, const float* img2, const float* taps, int win, int B, int C, int H, int W, float c1,
+                 float c2, const float* gout, float* d1, float* d2, void* stream);
+/* out[0] = weight * (1 - mean_b score[b]) (summed in index order by one thread), and its backward
+ * gl[b] = -g[0] * weight / B with g on the device: the loss form of the scores (vst.metrics.SSIMLoss). */
+int vst_ssim_loss(const float* score, int B, float weight, float* out, void* stream);
+int vst_ssim_loss_bwd(const float* g, int B, float weight, float* gl, void* stream);
 /* compute_histogram (AA/eval.py:38-46, np.bincount(img[:, :, ch].flatten(), minlength=256), without
  * its + 1): images = N x H x W x C uint8 (C = 1 or 3), hist = N x C x 256 int32, overwritten. */
 int vst_hist_u8(const void* images, void* hist, int N, int H, int W, int C, void* stream);

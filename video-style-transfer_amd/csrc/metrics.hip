@@ -9,7 +9,8 @@
 //   * vst_ssim: SSIMMetric.forward (AA/eval.py:191-223) -- five depthwise Gaussian windows over
 //     zero-padded planes, the SSIM map, mean over the plane then over the channels -- as one tile
 //     kernel: tile + halo of both images staged in LDS once, separable horizontal then vertical pass
-//     of the five moments, the map in registers, fp64 partial per tile;
+//     of the five moments, the map in registers, fp64 partial per tile; vst_ssim_c is the same with
+//     C1 and C2 as arguments (a data range other than 1; the gradient is csrc/ssim_grad.hip);
 //   * vst_hist_u8: np.bincount(channel, minlength=256) per image and channel (compute_histogram,
 //     AA/eval.py:38-46, the input of kl_loss) with integer LDS atomics per block.
 #include "vst_common.h"
@@ -188,9 +189,8 @@ struct SsimTaps {
 
 // the map of one pixel from its five windowed moments, in the reference's own operation order
 // (AA/eval.py:203-214), every product and sum rounded on its own (no contraction)
-__device__ __forceinline__ float ssim_pixel(float mu1, float mu2, float e11, float e22, float e12) {
+__device__ __forceinline__ float ssim_pixel(float mu1, float mu2, float e11, float e22, float e12, float C1, float C2) {
 #pragma clang fp contract(off)
-  const float C1 = (float)(0.01 * 0.01), C2 = (float)(0.03 * 0.03);  // the reference's Python doubles, to fp32
   const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu1_mu2 = mu1 * mu2;
   const float s1 = e11 - mu1_sq, s2 = e22 - mu2_sq, s12 = e12 - mu1_mu2;
   const float num = (2.f * mu1_mu2 + C1) * (2.f * s12 + C2);
@@ -204,8 +204,8 @@ __device__ __forceinline__ float ssim_pixel(float mu1, float mu2, float e11, flo
 // ds_read_b32 never meets one bank twice), then the five horizontally filtered planes of TH + 2R rows.
 template <int TW, int TH, int R>
 __global__ __launch_bounds__(MT) void ssim_tile_kernel(const float* __restrict__ img1, const float* __restrict__ img2,
-                                                       SsimTaps tp, int H, int W, float* __restrict__ map,
-                                                       double* __restrict__ partial) {
+                                                       SsimTaps tp, int H, int W, float c1, float c2,
+                                                       float* __restrict__ map, double* __restrict__ partial) {
   constexpr int WIN = 2 * R + 1, SW = TW + 2 * R, SH = TH + 2 * R, RPT = 4;
   static_assert(TW % 32 == 0 && TW * TH == MT * RPT, "tile shape");
   __shared__ float sx[SH * SW], sy[SH * SW];
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(MT) void ssim_tile_kernel(const float* __restrict__
   for (int q = 0; q < RPT; ++q) {
     const int gy = y0 + r0 + q;
     if (gx < W && gy < H) {
-      const float s = ssim_pixel(mom[0][q], mom[1][q], mom[2][q], mom[3][q], mom[4][q]);
+      const float s = ssim_pixel(mom[0][q], mom[1][q], mom[2][q], mom[3][q], mom[4][q], c1, c2);
       if (map) map[plane + (long)gy * W + gx] = s;
       acc += (double)s;
     }
@@ -298,15 +298,15 @@ __global__ __launch_bounds__(MT) void ssim_finish_kernel(const double* __restric
 
 template <int TW, int TH>
 int ssim_launch(const float* img1, const float* img2, const SsimTaps& tp, int win, int B, int C, int H, int W,
-                float* out, float* map, double* ws, hipStream_t st) {
+                float c1, float c2, float* out, float* map, double* ws, hipStream_t st) {
   const dim3 g((unsigned)ceil_div(W, TW), (unsigned)ceil_div(H, TH), (unsigned)(B * C));
   switch (win) {
-    case 1: ssim_tile_kernel<TW, TH, 0><<<g, MT, 0, st>>>(img1, img2, tp, H, W, map, ws); break;
-    case 3: ssim_tile_kernel<TW, TH, 1><<<g, MT, 0, st>>>(img1, img2, tp, H, W, map, ws); break;
-    case 5: ssim_tile_kernel<TW, TH, 2><<<g, MT, 0, st>>>(img1, img2, tp, H, W, map, ws); break;
-    case 7: ssim_tile_kernel<TW, TH, 3><<<g, MT, 0, st>>>(img1, img2, tp, H, W, map, ws); break;
-    case 9: ssim_tile_kernel<TW, TH, 4><<<g, MT, 0, st>>>(img1, img2, tp, H, W, map, ws); break;
-    default: ssim_tile_kernel<TW, TH, 5><<<g, MT, 0, st>>>(img1, img2, tp, H, W, map, ws); break;
+    case 1: ssim_tile_kernel<TW, TH, 0><<<g, MT, 0, st>>>(img1, img2, tp, H, W, c1, c2, map, ws); break;
+    case 3: ssim_tile_kernel<TW, TH, 1><<<g, MT, 0, st>>>(img1, img2, tp, H, W, c1, c2, map, ws); break;
+    case 5: ssim_tile_kernel<TW, TH, 2><<<g, MT, 0, st>>>(img1, img2, tp, H, W, c1, c2, map, ws); break;
+    case 7: ssim_tile_kernel<TW, TH, 3><<<g, MT, 0, st>>>(img1, img2, tp, H, W, c1, c2, map, ws); break;
+    case 9: ssim_tile_kernel<TW, TH, 4><<<g, MT, 0, st>>>(img1, img2, tp, H, W, c1, c2, map, ws); break;
+    default: ssim_tile_kernel<TW, TH, 5><<<g, MT, 0, st>>>(img1, img2, tp, H, W, c1, c2, map, ws); break;
   }
   ssim_finish_kernel<<<B, MT, 0, st>>>(ws, (int)(g.x * g.y), C, 1.0 / ((double)H * W), out);
   return vst_launch_status();
@@ -394,19 +394,26 @@ long vst_ssim_workspace(int B, int C, int H, int W) {
   return 8 * (long)B * C * (t0 > t1 ? t0 : t1);
 }
 
-int vst_ssim(const float* img1, const float* img2, const float* taps, int win, int B, int C, int H, int W, float* out,
-             float* map, void* workspace, int tile, void* stream) {
+int vst_ssim_c(const float* img1, const float* img2, const float* taps, int win, int B, int C, int H, int W, float c1,
+               float c2, float* out, float* map, void* workspace, int tile, void* stream) {
   VST_CHECK_ARG(img1 && img2 && taps && out && workspace && B > 0 && C > 0 && H > 0 && W > 0);
   VST_CHECK_ARG(win >= 1 && win <= SSIM_MAXWIN && (win & 1) == 1 && tile >= 0 && tile <= 2);
   VST_CHECK_ARG((long)B * C <= 65535 && (H + 15) / 16 <= 65535 && (long)H * W < (1L << 31));
-  VST_CHECK_ARG(((uintptr_t)workspace & 7) == 0);
+  VST_CHECK_ARG(((uintptr_t)workspace & 7) == 0 && c1 == c1 && c2 == c2);
   SsimTaps tp;
   for (int k = 0; k < SSIM_MAXWIN; ++k) tp.g[k] = k < win ? taps[k] : 0.f;
   hipStream_t st = (hipStream_t)stream;
   double* ws = static_cast<double*>(workspace);
   // tile 0: the shape tools/eval_bench.py measured faster at 436 x 1024
-  if (tile == 2) return ssim_launch<64, 16>(img1, img2, tp, win, B, C, H, W, out, map, ws, st);
-  return ssim_launch<32, 32>(img1, img2, tp, win, B, C, H, W, out, map, ws, st);
+  if (tile == 2) return ssim_launch<64, 16>(img1, img2, tp, win, B, C, H, W, c1, c2, out, map, ws, st);
+  return ssim_launch<32, 32>(img1, img2, tp, win, B, C, H, W, c1, c2, out, map, ws, st);
+}
+
+int vst_ssim(const float* img1, const float* img2, const float* taps, int win, int B, int C, int H, int W, float* out,
+             float* map, void* workspace, int tile, void* stream) {
+  // the reference's Python doubles (AA/eval.py:176-177), to fp32
+  return vst_ssim_c(img1, img2, taps, win, B, C, H, W, (float)(0.01 * 0.01), (float)(0.03 * 0.03), out, map, workspace,
+                    tile, stream);
 }
 
 int vst_hist_u8(const void* images, void* hist, int N, int H, int W, int C, void* stream) {

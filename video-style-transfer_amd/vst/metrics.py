@@ -1,7 +1,8 @@
 """Evaluation metrics on the MI355X: the temporal (warping) error of RT/utilities.py:194-240 and
 AA/exps_sintel.py:66-110, and SSIM / Gram distance / histogram KL / LPIPS of AA/eval.py, on the HIP
 kernels of csrc/metrics.hip and csrc/lpips.hip (the LPIPS model itself is vst.lpips).  As everywhere in this package there is no CPU path: tensors on the host raise
-`VstError`.
+`VstError`.  SSIM is also a differentiable score and a training loss (`ssim_scores`, `SSIMLoss`, on the fused
+backward of csrc/ssim_grad.hip); the metric entries stay forward only.
 
 Out of scope: SIFID (an InceptionV3 trunk whose weights are a download), RAFT flow
 estimation, and the three grey-level histogram metrics of AA/eval.py:111-164 (OpenCV's BGR2GRAY
@@ -159,6 +160,108 @@ def ssim(img1, img2, window_size=11, sigma=1.5, reduction="mean", return_map=Fal
         raise VstError(f"ssim: window_size must be odd and <= {SSIM_MAX_WINDOW}, got {window_size}")
     score, smap = _ssim_call(img1, img2, _gauss_1d(window_size, sigma).numpy(), reduction != "mean", return_map)
     return (score, smap) if return_map else score
+
+
+# ------------------------------------------------------------------------------------------------
+# SSIM as a differentiable score and a training loss
+def _ssim_constants(data_range):
+    """C1 = (0.01 L)^2, C2 = (0.03 L)^2 as Python doubles (the C entries take them as fp32): L = 1 gives
+    the metric's own constants bit for bit."""
+    return (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
+
+
+class _SSIMScoresFn(torch.autograd.Function):
+    """The (B,) per-image scores of `vst_ssim_c`; the backward is one `vst_ssim_bwd` launch, which
+    recomputes the moments (nothing but the two images is saved) and also gives img2's gradient when
+    img2 requires grad."""
+
+    @staticmethod
+    def forward(ctx, a, b, taps, c1, c2):
+        B, C, H, W = a.shape
+        out = torch.empty(B, dtype=torch.float32, device=a.device)
+        ws = torch.empty(max(1, lib.vst_ssim_workspace(B, C, H, W) // 8), dtype=torch.float64, device=a.device)
+        lib.vst_ssim_c(ptr(a), ptr(b), taps.ctypes.data, len(taps), B, C, H, W, c1, c2, ptr(out), None, ws.data_ptr(),
+                       SSIM_TILES["default"], stream())
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(a, b)
+        ctx.args = (taps, c1, c2)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None, None
+        a, b = ctx.saved_tensors
+        taps, c1, c2 = ctx.args
+        B, C, H, W = a.shape
+        d1 = torch.empty_like(a)
+        d2 = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        lib.vst_ssim_bwd(ptr(a), ptr(b), taps.ctypes.data, len(taps), B, C, H, W, c1, c2, ptr(g.contiguous()), ptr(d1),
+                         ptr(d2), stream())
+        return (d1 if ctx.needs_input_grad[0] else None), d2, None, None, None
+
+
+def ssim_scores(img1, img2, window_size=11, sigma=1.5, data_range=1.0):
+    """The (B,) per-image SSIM of two (B,C,H,W) fp32 device tensors with values in [0, data_range],
+    differentiable in img1 and -- when it requires grad -- in img2 (one fused backward kernel,
+    `vst_ssim_bwd`, for both).  `SSIMMetric` / `ssim` stay the forward-only metric; with data_range = 1
+    the scores here are theirs bit for bit.  Nothing is recorded when neither input requires grad or
+    grad mode is off."""
+    if window_size % 2 != 1 or not 1 <= window_size <= SSIM_MAX_WINDOW:
+        raise VstError(f"ssim_scores: window_size must be odd and <= {SSIM_MAX_WINDOW}, got {window_size}")
+    a = ops._check(img1, "img1", 4)
+    b = ops._check(img2, "img2", 4)
+    if a.shape != b.shape:
+        raise VstError(f"ssim_scores: shapes {tuple(a.shape)} and {tuple(b.shape)} differ")
+    taps = np.ascontiguousarray(_gauss_1d(window_size, sigma).numpy(), dtype=np.float32)
+    c1, c2 = _ssim_constants(data_range)
+    return _SSIMScoresFn.apply(a, b, taps, c1, c2)
+
+
+class _SSIMLossFn(torch.autograd.Function):
+    """weight * (1 - mean_b score[b]) as a 0-d tensor (`vst_ssim_loss` / `vst_ssim_loss_bwd`)."""
+
+    @staticmethod
+    def forward(ctx, score, weight):
+        out = torch.empty((), dtype=torch.float32, device=score.device)
+        lib.vst_ssim_loss(ptr(score), score.numel(), float(weight), ptr(out), stream())
+        ctx.args = (score.numel(), float(weight))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        B, weight = ctx.args
+        gl = torch.empty(B, dtype=torch.float32, device=g.device)
+        lib.vst_ssim_loss_bwd(ptr(g.contiguous()), B, weight, ptr(gl), stream())
+        return gl, None
+
+
+class SSIMLoss(nn.Module):
+    """SSIM as a training-loss term over what the trainers hold (fp32 planes in [0, data_range], 255
+    by default): `set_target(frames)` keeps the target (a video trainer's content frame, or the warped
+    previous output); `forward(pred)` returns `weight * (1 - mean_b SSIM(pred, target)_b)` as a 0-d
+    tensor, differentiable in pred, which composes with `ops.sum_scalars`."""
+
+    def __init__(self, window_size=11, sigma=1.5, data_range=255.0, weight=1.0):
+        super().__init__()
+        if window_size % 2 != 1 or not 1 <= window_size <= SSIM_MAX_WINDOW:
+            raise VstError(f"SSIMLoss: window_size must be odd and <= {SSIM_MAX_WINDOW}, got {window_size}")
+        self.window_size, self.sigma = int(window_size), float(sigma)
+        self.data_range, self.weight = float(data_range), float(weight)
+        self.target = None
+
+    def set_target(self, frames):
+        self.target = ops._check(frames, "frames", 4).detach()
+        return self
+
+    def forward(self, pred):
+        if self.target is None:
+            raise VstError("SSIMLoss: set_target(frames) first")
+        p = ops._check(pred, "pred", 4)
+        if p.shape != self.target.shape:
+            raise VstError(f"SSIMLoss: pred {tuple(p.shape)} does not match the target's {tuple(self.target.shape)}")
+        score = ssim_scores(p, self.target, self.window_size, self.sigma, self.data_range)
+        return _SSIMLossFn.apply(score, self.weight)
 
 
 # ------------------------------------------------------------------------------------------------
