@@ -320,8 +320,8 @@ int vst_instnorm_apply(const float* x, const double* partial, const float* w, co
                        float* y, float* stats, int N, int C, int HW, int S, float eps, int relu, void* stream);
 int vst_instnorm_tanh_frames(const float* x, const double* partial, const float* w, const float* b, void* frames,
                              int N, int HW, int S, float eps, int bgr, void* stream);
-/* out[c] (+)= sum_{n,i} x[n][c][i]; partial: N*C floats (conv bias gradient) */
-int vst_channel_sum(const float* x, float* out, float* partial, int N, int C, int HW, int accumulate, void* stream);
+/* out[c] (+)= sum_{n,i} x[n][c][i] (conv bias gradient), rounded to fp32 once; partial: N*C doubles */
+int vst_channel_sum(const float* x, float* out, double* partial, int N, int C, int HW, int accumulate, void* stream);
 
 /* ---- VGG MaxPool2d(2, 2) (RC/network.py:12-24 via torchvision features) -------------------- */
 int vst_maxpool2x2_fwd(const float* x, float* y, long NC, int H, int W, void* stream);

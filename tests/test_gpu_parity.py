@@ -263,6 +263,7 @@ def test_vgg_slice_fused_relu_backward():
                                             # the two-pass kernels: HW > 32768, and HW % 4 != 0
                                             (True, False, (1, 4, 256, 260)), (True, False, (1, 3, 101, 103))])
 def test_instance_norm(relu, res, shape):
+    # (per-element bounds against float64, every route boundary and mask mode: tests/test_gpu_norm.py)
     from vst import ops
 
     g = torch.Generator().manual_seed(3)

@@ -29,6 +29,10 @@ __device__ __forceinline__ T block_sum(T v, T* sh) {
   return s;
 }
 
+// 16-byte alignment of a tensor's base: with HW % 4 == 0 every plane then starts on a float4 (a view
+// into a larger buffer need not; the float4 forms below are taken only when every tensor they touch is)
+__host__ __device__ __forceinline__ bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 // The pre-activation (x - mean) * rstd * w + b with fixed rounding (no contraction left to the
 // compiler): the backward recomputes it from x to get the ReLU mask instead of reading y, and must
 // reproduce the forward's sign bit for bit.
@@ -48,7 +52,7 @@ __global__ __launch_bounds__(NT) void in_fwd_kernel(const float* __restrict__ x,
   const long plane = blockIdx.x;
   const int c = (int)(plane % C);
   const float* xp = x + plane * HW;
-  const bool v4 = (HW & 3) == 0;
+  const bool v4 = (HW & 3) == 0 && al16(x) && al16(y) && al16(res);
   const int n4 = HW / 4;
   double s1 = 0.0, s2 = 0.0;
   if (v4) {
@@ -140,7 +144,7 @@ __global__ __launch_bounds__(NT) void in_bwd_kernel(const float* __restrict__ gy
   const float* xp = x + plane * HW;
   const float* yp = y + plane * HW;
   const float mean = stats[2 * plane], rstd = stats[2 * plane + 1];
-  const bool v4 = (HW & 3) == 0;
+  const bool v4 = (HW & 3) == 0 && al16(gy) && al16(x) && al16(y) && al16(gx);
   const int n4 = HW / 4;
   const bool ymask = relu && y, amask = relu && !y;
   const float wc = w[c], bc = amask ? bias[c] : 0.f;
@@ -649,7 +653,8 @@ __global__ __launch_bounds__(SP_NT) void in_tanh_frames_kernel(const float* __re
 }
 
 // dst_k[c] (+)= sum_n partial[(n*C + c)*NP + k] for the non-null dst_k
-__global__ void sum_over_n_kernel(const float* __restrict__ partial, int N, int C, int NP, float* d0, float* d1,
+template <typename T>
+__global__ void sum_over_n_kernel(const T* __restrict__ partial, int N, int C, int NP, float* d0, float* d1,
                                   float* d2, int accumulate) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
@@ -662,20 +667,21 @@ __global__ void sum_over_n_kernel(const float* __restrict__ partial, int N, int 
   }
 }
 
-// per-plane sums: out[plane] = sum_i x[plane][i]
-__global__ __launch_bounds__(NTN) void plane_sum_kernel(const float* __restrict__ x, float* __restrict__ out, int HW) {
+// per-plane sums: out[plane] = sum_i x[plane][i], kept in fp64 (a plane sum rounded to fp32 before the
+// sum over n would round a channel's result N + 1 times instead of once)
+__global__ __launch_bounds__(NTN) void plane_sum_kernel(const float* __restrict__ x, double* __restrict__ out, int HW) {
   __shared__ double sh[NTN / 64];
   const long plane = blockIdx.x;
   const float* xp = x + plane * HW;
   double s = 0.0;
   for (int i = threadIdx.x; i < HW; i += NTN) s += xp[i];
   s = block_sum(s, sh);
-  if (threadIdx.x == 0) out[plane] = (float)s;
+  if (threadIdx.x == 0) out[plane] = s;
 }
 
 // plane_sum_kernel over float4 (HW % 4 == 0, 16-byte aligned x): two float4 loads in flight per
 // thread per iteration instead of one scalar (the config-5 bias gradients sum 512x1024 planes)
-__global__ __launch_bounds__(NTN) void plane_sum_vec_kernel(const float4* __restrict__ x, float* __restrict__ out,
+__global__ __launch_bounds__(NTN) void plane_sum_vec_kernel(const float4* __restrict__ x, double* __restrict__ out,
                                                             int HW4) {
   __shared__ double sh[NTN / 64];
   const float4* xp = x + (long)blockIdx.x * HW4;
@@ -691,7 +697,7 @@ __global__ __launch_bounds__(NTN) void plane_sum_vec_kernel(const float4* __rest
     s += ((double)a.x + a.y) + ((double)a.z + a.w);
   }
   s = block_sum(s, sh);
-  if (threadIdx.x == 0) out[blockIdx.x] = (float)s;
+  if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 
 }  // namespace
@@ -702,9 +708,10 @@ int vst_instnorm_fwd(const float* x, const float* w, const float* b, const float
                      int C, int HW, float eps, int relu, void* stream) {
   VST_CHECK_ARG(x && w && b && y && stats && N > 0 && C > 0 && HW > 0);
   hipStream_t st = (hipStream_t)stream;
-  if ((HW & 3) == 0 && HW <= NTN * 4 * 4)
+  const bool vec = (HW & 3) == 0 && al16(x) && al16(y) && al16(res);
+  if (vec && HW <= NTN * 4 * 4)
     in_fwd_reg_kernel<512, 4><<<N * C, 512, 0, st>>>(x, w, b, res, y, stats, C, HW, eps, relu);
-  else if ((HW & 3) == 0 && HW <= 1024 * 4 * 8)
+  else if (vec && HW <= 1024 * 4 * 8)
     in_fwd_reg_kernel<1024, 8><<<N * C, 1024, 0, st>>>(x, w, b, res, y, stats, C, HW, eps, relu);
   else
     in_fwd_kernel<IN_BIG_NT><<<N * C, IN_BIG_NT, 0, st>>>(x, w, b, res, y, stats, C, HW, eps, relu);
@@ -716,7 +723,6 @@ int vst_instnorm_fwd(const float* x, const float* w, const float* b, const float
 static bool split_args_ok(long planes, int HW, int S) {
   return planes > 0 && HW > 0 && S >= 1 && S <= VST_INSTNORM_MAX_CHUNKS && planes * S <= 0x7fffffffL;
 }
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int vst_instnorm_moments(const float* x, double* partial, int planes, int HW, int S, void* stream) {
   VST_CHECK_ARG(x && partial && split_args_ok(planes, HW, S) && ((uintptr_t)partial & 7) == 0);
@@ -753,25 +759,26 @@ int vst_instnorm_bwd(const float* gy, const float* x, const float* y, const floa
   VST_CHECK_ARG(gy && x && stats && w && gx && partial && N > 0 && C > 0 && HW > 0);
   VST_CHECK_ARG(!relu || y || b);
   hipStream_t st = (hipStream_t)stream;
-  if ((HW & 3) == 0 && HW <= NTN * 4 * 4)
+  const bool vec = (HW & 3) == 0 && al16(gy) && al16(x) && al16(y) && al16(gx);
+  if (vec && HW <= NTN * 4 * 4)
     in_bwd_reg_kernel<512, 4, true><<<N * C, 512, 0, st>>>(gy, x, y, b, stats, w, gx, partial, C, HW, relu);
-  else if ((HW & 3) == 0 && HW <= LDS_NT * 4 * LDS_V4)
+  else if (vec && HW <= LDS_NT * 4 * LDS_V4)
     in_bwd_lds_kernel<<<N * C, LDS_NT, 0, st>>>(gy, x, y, b, stats, w, gx, partial, C, HW, relu);
   else
     in_bwd_kernel<IN_BIG_NT><<<N * C, IN_BIG_NT, 0, st>>>(gy, x, y, b, stats, w, gx, partial, C, HW, relu);
-  sum_over_n_kernel<<<ceil_div(C, 256), 256, 0, st>>>(partial, N, C, 3, gw, gb, gbias_prev, accumulate);
+  sum_over_n_kernel<float><<<ceil_div(C, 256), 256, 0, st>>>(partial, N, C, 3, gw, gb, gbias_prev, accumulate);
   return vst_launch_status();
 }
 
-// out[c] (+)= sum_{n,i} x[n][c][i]   (conv bias gradient); partial: N*C floats workspace
-int vst_channel_sum(const float* x, float* out, float* partial, int N, int C, int HW, int accumulate, void* stream) {
-  VST_CHECK_ARG(x && out && partial && N > 0 && C > 0 && HW > 0);
+// out[c] (+)= sum_{n,i} x[n][c][i]   (conv bias gradient); partial: N*C doubles workspace
+int vst_channel_sum(const float* x, float* out, double* partial, int N, int C, int HW, int accumulate, void* stream) {
+  VST_CHECK_ARG(x && out && partial && N > 0 && C > 0 && HW > 0 && ((uintptr_t)partial & 7) == 0);
   hipStream_t st = (hipStream_t)stream;
   if ((HW & 3) == 0 && ((uintptr_t)x & 15) == 0)
     plane_sum_vec_kernel<<<N * C, NTN, 0, st>>>(reinterpret_cast<const float4*>(x), partial, HW / 4);
   else
     plane_sum_kernel<<<N * C, NTN, 0, st>>>(x, partial, HW);
-  sum_over_n_kernel<<<ceil_div(C, 256), 256, 0, st>>>(partial, N, C, 1, out, nullptr, nullptr, accumulate);
+  sum_over_n_kernel<double><<<ceil_div(C, 256), 256, 0, st>>>(partial, N, C, 1, out, nullptr, nullptr, accumulate);
   return vst_launch_status();
 }
 

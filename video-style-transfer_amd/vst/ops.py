@@ -871,8 +871,8 @@ def channel_sum(x, out=None):
     HW = x[0, 0].numel()
     acc = out is not None
     out = _empty((C,), x) if out is None else out
-    part = _empty((N * C,), x)
-    lib.vst_channel_sum(ptr(x), ptr(out), ptr(part), N, C, HW, int(acc), stream())
+    part = torch.empty((N * C,), device=x.device, dtype=torch.float64)
+    lib.vst_channel_sum(ptr(x), ptr(out), part.data_ptr(), N, C, HW, int(acc), stream())
     return out
 
 
