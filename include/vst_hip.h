@@ -173,6 +173,17 @@ int vst_conv_stem_u8(const void* frames, const float* w, const float* bias, floa
  * w: [Cout][3][3][3] (PyTorch layout).  The output-write-bound layer skips the unfold + K = 48 GEMM. */
 int vst_conv_cin3_k3(const float* x, const float* w, const float* b, float* out, int N, int H, int W, int Cout,
                      int reflect, int relu, void* stream);
+/* The AlexNet stem (torchvision alexnet.features[0:2], the first slice of AA/lpips/pretrained_networks.py:
+ * 57-95): the 11x11 stride-4 zero-pad-2 conv of a 3-channel image,
+ *   out[n][co][oy][ox] = [relu](b[co] + sum_{ci,kh,kw} w[co][ci][kh][kw] * xpad[n][ci][4 oy + kh][4 ox + kw]),
+ * x: [N][3][H][W] fp32, w: [Cout][3][11][11] (PyTorch layout), b may be NULL, out: [N][Cout][Ho][Wo] with
+ * Ho = (H + 4 - 11) / 4 + 1, Wo likewise (floor): trailing rows and columns that no window reaches are
+ * never read.  Exact fp32 on the VALU (no MFMA, no GEMM mode).  One fixed FMA order (from 0 over ci, then
+ * kh, then kw ascending, then + b; csrc/alex.hip), independent of N and of the launch geometry: image n of
+ * a batch is bitwise the image alone.  N in 1..65535, H >= 7, W >= 7 (any W: no W % 4 requirement), H W <
+ * 2^31, Cout in {16, 32, 48, 64}.  x, w, out: 4-byte aligned (every global access is one float). */
+int vst_conv_cin3_k11s4(const float* x, const float* w, const float* b, float* out, int N, int H, int W, int Cout,
+                        int relu, void* stream);
 int vst_unfold_kw(const float* src, float* out, int N, int C, int H, int Ws, int Wout, int K, int Cu, int sgn, int off,
                   int reflect, void* stream);
 int vst_pack_weight_kwu(const float* w, float* packed, int Cout, int Cin, int K, int Cu, int transposed, int Mpad,
@@ -331,6 +342,13 @@ int vst_maxpool2x2_bwd(const float* x, const float* gy, float* gx, long NC, int 
  * gx = [relu_mask: (x > 0) *] (pool_bwd(gy) + addend) in one pass; gy or addend may be NULL */
 int vst_maxpool2x2_bwd_add(const float* x, const float* gy, const float* addend, float* gx, long NC, int H, int W,
                            int relu_mask, void* stream);
+/* AlexNet's MaxPool2d(3, 2) (torchvision alexnet.features[2], [5]; no padding, floor mode), forward only:
+ *   out[nc][oy][ox] = max_{kh,kw in 0..2} x[nc][2 oy + kh][2 ox + kw],  Ho = (H - 3) / 2 + 1, Wo likewise;
+ * rows and columns past the last window are never read.  The nine values meet in window order (kh, then kw)
+ * under ATen's comparison (v > m or v is NaN, from -inf), so the result is
+ * torch.nn.functional.max_pool2d(x, 3, 2) bit for bit for any fp32 values.  x: NC planes of [H][W], out: NC
+ * planes of [Ho][Wo]; H, W >= 3, NC <= 2^31 - 1, H W < 2^31; 4-byte aligned. */
+int vst_maxpool3x3s2_fwd(const float* x, float* out, long NC, int H, int W, void* stream);
 
 /* ---- flow warp (RC/utilities.py:39-57) / occlusion mask (RC/utilities.py:60-90) ------------
  * warp_bwd scatters with float atomics into gx (zero it first or accumulate). */

@@ -1,5 +1,6 @@
-"""Drop-in MI355X implementation of the reference's `lpips` package (AA/lpips/) for its VGG trunk:
-`LPIPS(net="vgg")`, the default mode of AA/eval.py and the first two columns of AA/exps_image.py.
+"""Drop-in MI355X implementation of the reference's `lpips` package (AA/lpips/) for its VGG and AlexNet
+trunks: `LPIPS(net="vgg")`, the default mode of AA/eval.py and the first two columns of AA/exps_image.py,
+and `LPIPS()` / `LPIPS(net="alex")`, the package's own default.
 
 Same class names, constructor arguments, `forward(in0, in1, retPerLayer=False, normalize=False)` and
 state_dict keys as the reference (`scaling_layer.shift`, `net.slice1.0.weight` ..., `lin0.model.1.weight`
@@ -7,23 +8,30 @@ state_dict keys as the reference (`scaling_layer.shift`, `net.slice1.0.weight` .
 `load_state_dict(..., strict=False)` as it does there.  The forward runs HIP kernels only:
   * `vst_lpips_input`: `2 x - 1` / im2tensor and the ScalingLayer, both inputs into one [2N,3,H,W] batch;
   * the VGG16 trunk (torchvision features[0:30]) once over that batch, on the convolution and pooling
-    kernels `vst.reconet.network.Vgg16` runs (GEMM scope "lpips");
+    kernels `vst.reconet.network.Vgg16` runs (GEMM scope "lpips"); or the AlexNet trunk (torchvision
+    alexnet.features[0:12]): the 11x11 stride-4 stem on `vst_conv_cin3_k11s4` (exact fp32), the two
+    MaxPool2d(3, 2) on `vst_maxpool3x3s2_fwd`, conv2..5 on the same GEMM / halo routes;
   * `vst_lpips_head` per level: both normalisations, the squared difference, the 1x1 linear layer (or
     the channel sum of `lpips=False`) and the spatial mean in one pass over the two feature halves,
     the five levels summed by the kernel's accumulate flag; `spatial=True` upsamples the per-level maps
     with `ops.resize_bilinear(..., addend=...)`.
 `forward` / `forward_u8` are forward only, as the reference evaluates (`eval_mode`): inputs that require
-grad, `pnet_tune=True` and trunks other than VGG16 raise `VstError`.  Nothing synchronises with the host.
+grad, `pnet_tune=True` and the SqueezeNet trunk raise `VstError`.  Nothing synchronises with the host.
 
 As a training loss: `LPIPS.encode(in1)` caches the target's five features, `LPIPS.distance_to(target, in0)`
 is differentiable in in0 (`vgg16.forward_grad` records the trunk's data gradients, `vst_lpips_head_bwd` is
 the fused backward of the five heads, `vst_lpips_input_bwd` that of the input pass; the parameters stay
-frozen), and `PerceptualLoss` wraps both for [0,255] frames as a 0-d loss term.
+frozen), and `PerceptualLoss` wraps both for [0,255] frames as a 0-d loss term.  This form is the VGG
+trunk's only: the AlexNet trunk is forward only (no 3x3 stride-2 pool backward, no stride-4 data gradient),
+so `encode`, `encode_u8`, `distance_to` and `PerceptualLoss` raise `VstError` on an alex model.
 
 Weights.  The trunk takes `weights=`, a path to a local torchvision vgg16 state dict (the reference
 downloads IMAGENET1K_V1), else torchvision's default init.  The learned linear layers (1,472 floats)
 are not shipped: `model_path=None` looks for weights/v0.1/vgg.pth beside the `lpips` drop-in package
 (video-style-transfer_amd/adaattn/lpips/); copy the reference's AA/lpips/weights/v0.1/vgg.pth there.
+`net="alex"` likewise: a local torchvision alexnet state dict for the trunk, and weights/v0.1/alex.pth
+(1,152 floats) from the reference's AA/lpips/weights/v0.1/alex.pth.  An alex input is at least 31 x 31
+(the level grids are then 7, 3, 1, 1, 1); a VGG input at least 16 x 16.
 """
 import os
 from collections import namedtuple
@@ -36,15 +44,17 @@ from .. import ops
 from .._lib import VstError, lib, ptr, stream
 from ..reconet.network import _load_torchvision_features, run_vgg_slice, vgg_features
 
-__all__ = ["LPIPS", "LPIPSTarget", "PerceptualLoss", "ScalingLayer", "NetLinLayer", "vgg16", "normalize_tensor",
+__all__ = ["LPIPS", "LPIPSTarget", "PerceptualLoss", "ScalingLayer", "NetLinLayer", "vgg16", "alexnet", "normalize_tensor",
            "spatial_average", "upsample", "im2tensor", "load_image"]
 
 # torchvision VGG16 "D" features[0:30]
 _VGG16_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512]
 VggOutputs = namedtuple("VggOutputs", ["relu1_2", "relu2_2", "relu3_3", "relu4_3", "relu5_3"])
+AlexnetOutputs = namedtuple("AlexnetOutputs", ["relu1", "relu2", "relu3", "relu4", "relu5"])
 # where `model_path=None` looks for the linear layers: beside the `lpips` drop-in package
 DROPIN_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "adaattn", "lpips")
 MIN_SIDE = 16  # four 2x2 pools
+MIN_SIDE_ALEX = 31  # the stem's 7 x 7 grid, then two 3x3 stride-2 pools: 7 -> 3 -> 1
 # the ScalingLayer's per-channel constants (AA/lpips/lpips.py:167-168; vst_lpips_input carries the same)
 SHIFT, SCALE = (-0.030, -0.088, -0.188), (0.458, 0.448, 0.450)
 
@@ -192,6 +202,78 @@ class vgg16(nn.Module):
         return VggOutputs(*outs)
 
 
+def alexnet_features():
+    """torchvision's alexnet.features[0:12] (the last MaxPool2d, index 12, is not part of the trunk)."""
+    return [nn.Conv2d(3, 64, kernel_size=11, stride=4, padding=2), nn.ReLU(inplace=True),
+            nn.MaxPool2d(kernel_size=3, stride=2),
+            nn.Conv2d(64, 192, kernel_size=5, padding=2), nn.ReLU(inplace=True),
+            nn.MaxPool2d(kernel_size=3, stride=2),
+            nn.Conv2d(192, 384, kernel_size=3, padding=1), nn.ReLU(inplace=True),
+            nn.Conv2d(384, 256, kernel_size=3, padding=1), nn.ReLU(inplace=True),
+            nn.Conv2d(256, 256, kernel_size=3, padding=1), nn.ReLU(inplace=True)]
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def run_alex_slice(seq, x):
+    """Forward of one AlexNet slice on HIP kernels, by the modules' own kernel_size / stride / padding:
+    the 3-channel 11x11 stride-4 pad-2 conv on the stem kernel, MaxPool2d(3, 2) on the 3x3 pool kernel,
+    the stride-1 convs (5x5 pad 2, 3x3 pad 1) through ops.conv2d; a Conv2d's ReLU is fused into it."""
+    mods = list(seq.children())
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        if isinstance(m, nn.Conv2d):
+            relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+            geom = (m.in_channels, _pair(m.kernel_size), _pair(m.stride), _pair(m.padding))
+            if geom == (3, (11, 11), (4, 4), (2, 2)):
+                x = ops.conv_cin3_k11s4(x, m.weight, m.bias, relu=relu)
+            elif geom[2] == (1, 1) and geom[1][0] == geom[1][1] and geom[3] == (geom[1][0] // 2,) * 2:
+                x = ops.conv2d(x, m.weight, m.bias, stride=1, pad=geom[3][0], pad_mode="zero", act="relu" if relu else None)
+            else:
+                raise VstError(f"lpips: no kernel for {m} on the AlexNet trunk")
+            i += 2 if relu else 1
+        elif isinstance(m, nn.MaxPool2d):
+            if (_pair(m.kernel_size), _pair(m.stride), _pair(m.padding), m.ceil_mode) != ((3, 3), (2, 2), (0, 0), False):
+                raise VstError(f"lpips: no kernel for {m} on the AlexNet trunk")
+            x = ops.maxpool3x3s2(x)
+            i += 1
+        else:
+            raise VstError(f"lpips: unsupported AlexNet layer {m}")
+    return x
+
+
+class alexnet(nn.Module):
+    """AA/lpips/pretrained_networks.py:57-95: torchvision alexnet features[0:12] in five slices (indices
+    (0,1) (2..4) (5..7) (8,9) (10,11)); forward returns relu1 .. relu5.  `weights`: a local torchvision
+    alexnet state dict (no download).  Forward only: there is no `forward_grad`."""
+
+    def __init__(self, requires_grad=False, pretrained=True, weights=None):
+        super().__init__()
+        if requires_grad:
+            raise VstError("lpips: the trunk is forward only (pnet_tune / requires_grad is not carried)")
+        feats = alexnet_features()
+        _load_torchvision_features(feats, weights)
+        self.N_slices = 5
+        for s, (lo, hi) in enumerate(((0, 2), (2, 5), (5, 8), (8, 10), (10, 12))):
+            seq = nn.Sequential()
+            for x in range(lo, hi):
+                seq.add_module(str(x), feats[x])
+            setattr(self, f"slice{s + 1}", seq)
+        for p in self.parameters():
+            p.requires_grad = False
+
+    def forward(self, X):
+        outs, h = [], X
+        with torch.no_grad(), ops.gemm_scope("lpips"):
+            for s in range(self.N_slices):
+                h = run_alex_slice(getattr(self, f"slice{s + 1}"), h)  # slices 2 and 3 start with their pool
+                outs.append(h)
+        return AlexnetOutputs(*outs)
+
+
 class _InputFn(torch.autograd.Function):
     """`vst_lpips_input` over fp32 planes (normalize: 0 as is, 1 `2 x - 1`, 2 `2 (x / 255) - 1`) with its
     backward `vst_lpips_input_bwd`."""
@@ -286,14 +368,15 @@ class LPIPSTarget:
 
 
 class LPIPS(nn.Module):
-    """AA/lpips/lpips.py:24-161 for net="vgg" / "vgg16"."""
+    """AA/lpips/lpips.py:24-161 for net="alex" (the default) and net="vgg" / "vgg16"."""
 
     def __init__(self, pretrained=True, net="alex", version="0.1", lpips=True, spatial=False, pnet_rand=False,
                  pnet_tune=False, use_dropout=True, model_path=None, eval_mode=True, verbose=True, weights=None):
         super().__init__()
-        if net not in ("vgg", "vgg16"):
-            raise VstError(f"lpips: trunk {net!r} is not carried, only 'vgg' / 'vgg16': AlexNet and SqueezeNet need "
-                           "11x11 stride-4 convolutions and 3x3 stride-2 max-pools, which this library does not have")
+        if net not in ("vgg", "vgg16", "alex"):
+            raise VstError(f"lpips: trunk {net!r} is not carried, only 'alex' and 'vgg' / 'vgg16': beyond the VGG "
+                           "kernels the library has AlexNet's 11x11 stride-4 stem and 3x3 stride-2 floor-mode "
+                           "max-pool, not SqueezeNet's stride-2 stem, ceil-mode pools and fire modules")
         if pnet_tune:
             raise VstError("lpips: pnet_tune=True is not carried (forward only, as the reference evaluates)")
         if verbose:
@@ -306,9 +389,11 @@ class LPIPS(nn.Module):
         self.lpips = lpips
         self.version = version
         self.scaling_layer = ScalingLayer()
-        self.chns = [64, 128, 256, 512, 512]
+        self.alex = net == "alex"
+        self.chns = [64, 192, 384, 256, 256] if self.alex else [64, 128, 256, 512, 512]
         self.L = len(self.chns)
-        self.net = vgg16(pretrained=not self.pnet_rand, requires_grad=self.pnet_tune, weights=weights)
+        net_type = alexnet if self.alex else vgg16
+        self.net = net_type(pretrained=not self.pnet_rand, requires_grad=self.pnet_tune, weights=weights)
         if lpips:
             for k in range(self.L):
                 setattr(self, f"lin{k}", NetLinLayer(self.chns[k], use_dropout=use_dropout))
@@ -317,9 +402,11 @@ class LPIPS(nn.Module):
                 if model_path is None:
                     model_path = default_model_path(version, net)
                 if not os.path.isfile(model_path):
-                    raise VstError(f"lpips: the linear-layer weights {model_path} are missing; this repository does "
-                                   "not ship them: copy the reference's lpips/weights/v%s/vgg.pth there, pass "
-                                   "model_path=, or build with pretrained=False" % version)
+                    ref_file = "lpips/weights/v%s/%s.pth" % (version, "alex" if self.alex else "vgg")
+                    trunk = "AlexNet (11x11 stride-4 stem)" if self.alex else "VGG16"
+                    raise VstError(f"lpips: the linear-layer weights {model_path} of the {trunk} trunk are missing; "
+                                   f"this repository does not ship them: copy the reference's {ref_file} there, pass "
+                                   "model_path=, or build with pretrained=False")
                 if verbose:
                     print(f"lpips: linear layers from {model_path}")
                 self.load_state_dict(torch.load(model_path, map_location="cpu", weights_only=True), strict=False)
@@ -328,8 +415,9 @@ class LPIPS(nn.Module):
 
     # -- inputs ----------------------------------------------------------------------------------
     def _batch(self, N, H, W, like, sides=2):
-        if H < MIN_SIDE or W < MIN_SIDE:
-            raise VstError(f"lpips: images must be at least {MIN_SIDE} x {MIN_SIDE} (four 2x2 pools), got {H} x {W}")
+        side, why = (MIN_SIDE_ALEX, "the stride-4 stem and two 3x3 stride-2 pools") if self.alex else (MIN_SIDE, "four 2x2 pools")
+        if H < side or W < side:
+            raise VstError(f"lpips: images must be at least {side} x {side} ({why}), got {H} x {W}")
         return torch.empty((sides * N, 3, H, W), dtype=torch.float32, device=like.device)
 
     def forward(self, in0, in1, retPerLayer=False, normalize=False):
@@ -363,12 +451,18 @@ class LPIPS(nn.Module):
         return self._distance(x, N, H, W, retPerLayer)
 
     # -- the training-loss form: a cached target and a distance differentiable in in0 --------------
+    def _forward_only(self, what):
+        if self.alex:
+            raise VstError(f"lpips: {what} is not carried on net='alex': the AlexNet trunk is forward only (no 3x3 "
+                           "stride-2 pool backward, no stride-4 data gradient); use forward / forward_u8, or net='vgg'")
+
     def _target(self, x, N, H, W):
         return LPIPSTarget([f.detach() for f in self.net(x)], N, H, W)
 
     def encode(self, in1, normalize=False):
         """The target side of `distance_to`, computed once under no_grad: in1 as `forward` takes it.
         A video trainer encodes the content frame once and reuses it for every prediction."""
+        self._forward_only("encode")
         b = ops._check(in1, "in1", 4)
         if b.shape[1] != 3:
             raise VstError(f"lpips: the target must be (N,3,H,W), got {tuple(b.shape)}")
@@ -379,6 +473,7 @@ class LPIPS(nn.Module):
 
     def encode_u8(self, frames, bgr=True):
         """`encode` from (N,H,W,3) uint8 device frames (bgr: cv2's channel order), as `forward_u8`."""
+        self._forward_only("encode_u8")
         if frames.dim() != 4 or frames.shape[-1] != 3:
             raise VstError(f"lpips: frames must be (N,H,W,3) uint8, got {tuple(frames.shape)}")
         N, H, W, _ = frames.shape
@@ -393,6 +488,7 @@ class LPIPS(nn.Module):
         images only, the five fused heads and their fused backward (`vst_lpips_head_bwd`) carry the
         gradient into the trunk's data gradients.  Per-layer values (retPerLayer) are detached.  Nothing
         is recorded when in0 does not require grad or grad mode is off."""
+        self._forward_only("distance_to")
         if self.spatial:
             raise VstError("lpips: distance_to carries no per-pixel map (spatial=True); use forward")
         if not isinstance(target, LPIPSTarget):
@@ -449,6 +545,7 @@ class PerceptualLoss(nn.Module):
         super().__init__()
         if not isinstance(model, LPIPS):
             raise VstError("PerceptualLoss: model must be a vst.lpips.LPIPS")
+        model._forward_only("PerceptualLoss")
         self.model = model
         self.weight = float(weight)
         self.target = None

@@ -1216,6 +1216,44 @@ def maxpool2x2(x, relu_mask=False):
     return MaxPool2x2Fn.apply(x, relu_mask)
 
 
+def maxpool3x3s2(x):
+    """MaxPool2d(3, 2) (AlexNet's: no padding, floor mode) on vst_maxpool3x3s2_fwd, bitwise torch's.
+    Forward only: an input that requires grad raises."""
+    x = _check(x, "maxpool3x3s2 input", 4)
+    if x.requires_grad and torch.is_grad_enabled():
+        raise VstError("maxpool3x3s2: forward only (there is no 3x3 stride-2 pool backward)")
+    N, C, H, W = x.shape
+    if H < 3 or W < 3:
+        raise VstError(f"maxpool3x3s2: planes must be at least 3 x 3, got {H} x {W}")
+    y = _empty((N, C, (H - 3) // 2 + 1, (W - 3) // 2 + 1), x)
+    lib.vst_maxpool3x3s2_fwd(ptr(x), ptr(y), N * C, H, W, stream())
+    return y
+
+
+def conv_cin3_k11s4(x, w, b=None, relu=False):
+    """The AlexNet stem: Conv2d(3, Cout, 11, stride 4, padding 2) [+ ReLU] of (N,3,H,W) fp32 planes on
+    vst_conv_cin3_k11s4 (exact fp32 VALU, one fixed FMA order; image-space inputs get fp32 products, as
+    gemm_role("fwd_img") gives the GEMM stems).  Forward only."""
+    x = _check(x, "conv_cin3_k11s4 input", 4)
+    if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (b is not None and b.requires_grad)):
+        raise VstError("conv_cin3_k11s4: forward only (there is no stride-4 data or weight gradient)")
+    N, C, H, W = x.shape
+    w = w.detach().contiguous()
+    Cout = w.shape[0]
+    if C != 3 or tuple(w.shape) != (Cout, 3, 11, 11) or (b is not None and tuple(b.shape) != (Cout,)):
+        raise VstError(f"conv_cin3_k11s4: x{tuple(x.shape)} w{tuple(w.shape)}")
+    if H < 7 or W < 7:
+        raise VstError(f"conv_cin3_k11s4: the image must be at least 7 x 7, got {H} x {W}")
+    bias = b.detach().contiguous() if b is not None else None
+    Ho, Wo = (H + 4 - 11) // 4 + 1, (W + 4 - 11) // 4 + 1
+    out = _empty((N, Cout, Ho, Wo), x)
+    tok = kprof.begin(2.0 * N * Cout * Ho * Wo * 363, 4.0 * (x.numel() + out.numel() + w.numel()),
+                      ("cin3_k11s4", N, Cout, 3, H, W), None)
+    lib.vst_conv_cin3_k11s4(ptr(x), ptr(w), ptr(bias), ptr(out), N, H, W, Cout, int(bool(relu)), stream())
+    kprof.end(tok, family="thin")  # (a VALU kernel: outside the MFMA families' rooflines)
+    return out
+
+
 class FeaturePoolFn(Function):
     """A VGG slice output h (a ReLU output) that is both a loss feature and the next slice's
     MaxPool2d(2, 2) input (RC/network.py:33-40 slice boundaries): returns (h, maxpool(h)); the
